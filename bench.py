@@ -39,6 +39,16 @@ The JSON line also carries
   roofline_kernels, roofline_step: both sweeps of each state (bytes, event time, counter traffic, VALU share).
 --settle K times a developed flow, --variant M an A/B kernel instance, --ablate the
 section table of DESIGN.md section 4.4 (stderr).
+
+A plain run (no --full) is lean: set-up, W warm-up steps, exactly K timed steps (one block), the outputs if
+--dump-outputs DIR is given, the line.  `reps` is 1 and `cold_block`, `settled`, `with_bodies` and `cpu_baseline`
+are null (the DFSPH line's `runahead_ab` too).  --full adds everything else listed above: the repeated blocks until
+--min-seconds, the cold block, the settled state, the with-bodies workload, the CPU baseline and the DFSPH run-ahead A/B.
+
+--dump-outputs DIR writes what the timed path computed in its last step -- the particle arrays x, v, density and
+pressure a caller of WCSPHSolver.step() reads back -- as DIR/<name>.npy (float32), rows ordered by persistent particle id
+so that two builds compare element by element.  Above 64 MB in all, a fixed seeded sample of the particles is written
+instead, with their ids in DIR/sample_ids.npy (float64).
 """
 from __future__ import annotations
 
@@ -223,6 +233,34 @@ def with_bodies(args, local_rank, immerse_steps=300):
     return out
 
 
+DUMP_FIELDS = ("x", "v", "density", "pressure")
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(ps, out_dir):
+    """The arrays a caller of the timed path reads back after its last step, as out_dir/<name>.npy (float32), rows in
+    persistent-id order.  Above DUMP_BUDGET_BYTES in all, a fixed seeded sample of the particles (same rows in every
+    array; their ids in sample_ids.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    pid = ps.pid.to_numpy()
+    n = pid.shape[0]
+    arrays = {}
+    for name in DUMP_FIELDS:
+        a = getattr(ps, name).to_numpy()
+        by_pid = np.empty_like(a)
+        by_pid[pid] = a
+        arrays[name] = by_pid.astype(np.float32, copy=False)
+    row_bytes = sum(a.itemsize * (a.size // n) for a in arrays.values())
+    if row_bytes * n > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // (row_bytes + 8)
+        ids = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[ids]) for k, a in arrays.items()}
+        arrays["sample_ids"] = ids.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -237,10 +275,10 @@ def main():
                     help="run this many untimed steps first, so that the timed ones see a developed flow (dam-break front, "
                          "sloshing, compression at the walls) instead of the initial lattice")
     ap.add_argument("--settled-after", type=int, default=2000,
-                    help="the default line also times the box after this many further untimed steps (`settled` object); 0 = skip")
+                    help="--full: the line also times the box after this many further untimed steps (`settled` object); 0 = skip")
     ap.add_argument("--min-seconds", type=float, default=0.5,
-                    help="each state is timed for at least this long: from rest by repeating the K-step block from the re-uploaded "
-                         "initial state (`reps`), settled as one longer block")
+                    help="--full: each state is timed for at least this long: from rest by repeating the K-step block from the "
+                         "re-uploaded initial state (`reps`), settled as one longer block")
     ap.add_argument("--max-reps", type=int, default=80)
     ap.add_argument("--preheat-ms", type=float, default=50.0,
                     help="untimed GPU work (a matrix product loop on the same device, nothing of the solver's) right before "
@@ -259,7 +297,7 @@ def main():
                     help="--gpus N: wall-clock budget of the supplementary c4_dambreak object; when it is exceeded the finished "
                          "tiled line is printed with c4_dambreak = {error: watchdog, stage: ...}")
     ap.add_argument("--with-bodies", type=int, default=1,
-                    help="the default line also times the armadillo_bath_dynamic.json equivalent (1.72 M fluid + 3 dynamic bodies, "
+                    help="--full: the line also times the armadillo_bath_dynamic.json equivalent (1.72 M fluid + 3 dynamic bodies, "
                          "two-way coupling) once the bodies are immersed: `with_bodies` object (0 = skip)")
     ap.add_argument("--gather-impl", type=int, default=1)
     ap.add_argument("--brick-shape", type=int, default=0)
@@ -271,14 +309,23 @@ def main():
     ap.add_argument("--df-fuse-error", type=int, default=1, choices=[0, 1],
                     help="SPH_OPT_DF_FUSE_ERROR (--solver dfsph): 1 (default) = the refresh sweep of a solver iteration reduces the density error "
                          "itself, 0 = a streaming kernel re-reads the particles (A/B)")
-    ap.add_argument("--cpu-steps", type=int, default=10, help="CPU-oracle sample size (0 = skip the baseline leg)")
+    ap.add_argument("--cpu-steps", type=int, default=10, help="--full: CPU-oracle sample size (0 = skip the baseline leg)")
     ap.add_argument("--sweep", action="store_true", help="also time every gather variant (stderr table)")
     ap.add_argument("--time-every", type=int, default=8,
                     help="per-phase HIP events (breakdown_ms, roofline.avg_launch_ms) in every k-th step of the timed region: an "
                          "event record is a packet between two kernels, five per step cost 4 %% of the step (k = 1), k = 8 costs 0.5 %%")
     ap.add_argument("--ablate", action="store_true", help="profiling: time the sweeps with sections skipped (stderr)")
     ap.add_argument("--ablate-mask", type=int, default=0, help="profiling: run the whole bench with this ablation mask (results invalid)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline block: repeated blocks until --min-seconds, the cold block, the settled "
+                         "state, the with-bodies workload, the CPU baseline, the DFSPH run-ahead A/B (a plain run times one "
+                         "block of exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the particle arrays of the last timed step (x, v, density, pressure; float32, by persistent id) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is a single-GPU option (--gpus 1)")
     if args.ablate or args.ablate_mask:
         # section ablation lives in the PROFILING build of the library only (csrc: -DSPH_PROFILE); build / load that one
         os.environ["SPH_HIP_LIB_VARIANT"] = "profile"
@@ -400,25 +447,39 @@ def main():
         solver.dt[None] = CFG["timeStepSize"]
     if args.solver == "dfsph":
         import numpy as np
-        pid0 = ps.pid.to_numpy()
-        x_by_pid = np.empty_like(ps.x.to_numpy()); x_by_pid[pid0] = ps.x.to_numpy()
-        v_by_pid = np.empty_like(ps.v.to_numpy()); v_by_pid[pid0] = ps.v.to_numpy()
+        if args.full:
+            pid0 = ps.pid.to_numpy()
+            x_by_pid = np.empty_like(ps.x.to_numpy()); x_by_pid[pid0] = ps.x.to_numpy()
+            v_by_pid = np.empty_like(ps.v.to_numpy()); v_by_pid[pid0] = ps.v.to_numpy()
         it0 = solver.stats()
         dt, tm = run(args.gather_impl, args.brick_shape, 1, args.steps, args.warmup)
         it1 = solver.stats()
-        # A/B on the same box over the SAME steps (the run is deterministic: the initial state is restored by persistent id):
-        # the solver loops running AHEAD of their convergence tests (SPH_OPT_DF_RUNAHEAD 1: iteration k + 1 enqueued before
-        # the host waits for iteration k's device-side test) against the default above (enqueue, wait, decide)
-        pid = ps.pid.to_numpy()
-        ps.x.from_numpy(x_by_pid[pid]); ps.v.from_numpy(v_by_pid[pid])
-        solver.initialize()
-        ps.set_option(_lib.OPT_DF_RUNAHEAD, 1)
-        dt_ab1, _ = run(args.gather_impl, args.brick_shape, 1, args.steps, args.warmup)
-        it2 = solver.stats()
-        ps.set_option(_lib.OPT_DF_RUNAHEAD, 0)
-        dt_ab0 = dt
-        same_counts = (it2["total_iterations_v"] - it1["total_iterations_v"] == it1["total_iterations_v"] - it0["total_iterations_v"] and
-                       it2["total_iterations"] - it1["total_iterations"] == it1["total_iterations"] - it0["total_iterations"])
+        if args.dump_outputs:
+            dump_outputs(ps, args.dump_outputs)
+        runahead_ab = None
+        if args.full:
+            # A/B on the same box over the SAME steps (the run is deterministic: the initial state is restored by persistent id):
+            # the solver loops running AHEAD of their convergence tests (SPH_OPT_DF_RUNAHEAD 1: iteration k + 1 enqueued before
+            # the host waits for iteration k's device-side test) against the default above (enqueue, wait, decide)
+            pid = ps.pid.to_numpy()
+            ps.x.from_numpy(x_by_pid[pid]); ps.v.from_numpy(v_by_pid[pid])
+            solver.initialize()
+            ps.set_option(_lib.OPT_DF_RUNAHEAD, 1)
+            dt_ab1, _ = run(args.gather_impl, args.brick_shape, 1, args.steps, args.warmup)
+            it2 = solver.stats()
+            ps.set_option(_lib.OPT_DF_RUNAHEAD, 0)
+            dt_ab0 = dt
+            same_counts = (it2["total_iterations_v"] - it1["total_iterations_v"] == it1["total_iterations_v"] - it0["total_iterations_v"] and
+                           it2["total_iterations"] - it1["total_iterations"] == it1["total_iterations"] - it0["total_iterations"])
+            runahead_ab = {"ms_per_step_host_round_trip_per_iteration": round(dt_ab0 / args.steps * 1e3, 4),
+                           "ms_per_step_run_ahead": round(dt_ab1 / args.steps * 1e3, 4),
+                           "same_iteration_counts": bool(same_counts),
+                           "note": "the same W + K steps from the restored initial state with SPH_OPT_DF_RUNAHEAD 1; "
+                                   "host_round_trip_per_iteration = the line's own block (the default).  The second block starts "
+                                   "from the same positions and velocities in ANOTHER particle order (the one the first block ended in; "
+                                   "the stable sort keeps ties in their previous order), so its f32 sums differ in the last bit and "
+                                   "same_iteration_counts holds only until round-off moves one convergence test (~40 steps at 1.75 M); "
+                                   "bit-identity of the two modes on one order: test_dfsph_solver_loops_running_ahead_of_their_convergence_tests"}
         k = max(int(tm.steps), 1)
         iv = (it1["total_iterations_v"] - it0["total_iterations_v"]) / (args.warmup + args.steps)
         ip = (it1["total_iterations"] - it0["total_iterations"]) / (args.warmup + args.steps)
@@ -437,15 +498,7 @@ def main():
                       "neighbour_sweeps_per_step": round(sweeps, 2),
                       "ms_per_sweep": round((tm.neighbour_ms + tm.force_ms) / k / sweeps, 4),
                       "simulated_time_per_wall_second": round(args.steps / dt * DFSPH_DT, 3),
-                      "runahead_ab": {"ms_per_step_host_round_trip_per_iteration": round(dt_ab0 / args.steps * 1e3, 4),
-                                      "ms_per_step_run_ahead": round(dt_ab1 / args.steps * 1e3, 4),
-                                      "same_iteration_counts": bool(same_counts),
-                                      "note": "the same W + K steps from the restored initial state with SPH_OPT_DF_RUNAHEAD 1; "
-                                              "host_round_trip_per_iteration = the line's own block (the default).  The second block starts "
-                                              "from the same positions and velocities in ANOTHER particle order (the one the first block ended in; "
-                                              "the stable sort keeps ties in their previous order), so its f32 sums differ in the last bit and "
-                                              "same_iteration_counts holds only until round-off moves one convergence test (~40 steps at 1.75 M); "
-                                              "bit-identity of the two modes on one order: test_dfsph_solver_loops_running_ahead_of_their_convergence_tests"}},
+                      "runahead_ab": runahead_ab},
             "roofline": None,
         }
         # The step is ~37 neighbour sweeps over unchanged positions; all but the first read the neighbour lists.  Algorithmic
@@ -483,7 +536,7 @@ def main():
                                 "avg_launch_ms": ms_sweep, "counters": traffic_note, "traffic_by_kernel": per_kernel,
                                 "note": "gather sweeps are VALU- / vector-memory-bound, not HBM-bound (DESIGN.md section 4)"}
         ps.close()
-        line["cpu_baseline"] = cpu_baseline(sd, args.cpu_steps) if args.cpu_steps > 0 else None
+        line["cpu_baseline"] = cpu_baseline(sd, args.cpu_steps) if args.full and args.cpu_steps > 0 else None
         print(json.dumps(line), flush=True)
         return
     # ---- the headline line: state A = from rest, state B = the same box settled ----
@@ -563,12 +616,12 @@ def main():
                 "mean_cell_occupancy": round(N / max(st.nonempty_cells, 1), 2)},
         }
 
-    # State A.  The contract's timed region: W untimed + exactly K timed steps.  K = 20 is 8 ms of GPU time, too short
-    # for anything outside this process to see, so the block is REPEATED from the same initial state (positions and
-    # velocities re-uploaded by persistent id, untimed) until >= 0.5 s of timed steps have run; the line reports the
-    # mean over the repetitions (`reps`) and the first one beside it.
+    # State A.  The contract's timed region: W untimed + exactly K timed steps.  A plain run times that one block.  With
+    # --full, since K = 20 is 8 ms of GPU time, too short for anything outside this process to see, the block is REPEATED
+    # from the same initial state (positions and velocities re-uploaded by persistent id, untimed) until >= 0.5 s of timed
+    # steps have run; the line reports the mean over the repetitions (`reps`) and the first one beside it.
     import numpy as np
-    restore = args.settle == 0 and not args.ablate_mask
+    restore = args.full and args.settle == 0 and not args.ablate_mask
     if restore:
         x0, v0 = ps.x.to_numpy(), ps.v.to_numpy()
         pid0 = ps.pid.to_numpy()
@@ -593,6 +646,8 @@ def main():
         pid = ps.pid.to_numpy()
         ps.x.from_numpy(x_by_pid[pid]); ps.v.from_numpy(v_by_pid[pid])
         solver.initialize()
+    if args.dump_outputs:
+        dump_outputs(ps, args.dump_outputs)
     dt_mean = sum(b[0] for b in blocks) / len(blocks)
     tm_sum = _lib.SphTimings()
     for _, tm in blocks:
@@ -626,7 +681,8 @@ def main():
         "config": {"workload": args.workload, "particles": N, "cells": G, "dt": CFG["timeStepSize"],
                    "gather_impl": args.gather_impl, "brick_shape": args.brick_shape, "fused": args.fused,
                    "kernel_variant": ps.get_option(_lib.OPT_KERNEL_VARIANT), "brick_records": args.brick_records, "parallelism": "1 GPU",
-                   "settle_steps": args.settle, "state": "settled" if args.settle else "from rest (steps W..W+K of the initial lattice)"},
+                   "settle_steps": args.settle, "state": "settled" if args.settle else "from rest (steps W..W+K of the initial lattice)",
+                   "full": args.full},
         "reps": reps, "timed_seconds": round(t_timed, 3),
         "first_rep": {"value": first["value"], "ms_per_step": first["ms_per_step"]},
         "preheat_ms": 0.0 if _HEAT.get("broken") else args.preheat_ms,
@@ -672,7 +728,7 @@ def main():
     # State B: the same box after `--settled-after` untimed steps (the fluid has sunk to its rest density: 10 particles
     # per cell instead of the lattice's 8, 43 neighbours instead of 33) -- what a long run sees.  One contiguous block
     # of at least K steps and at least --min-seconds.
-    if args.settle == 0 and args.settled_after > 0 and not args.ablate_mask:
+    if args.full and args.settle == 0 and args.settled_after > 0 and not args.ablate_mask:
         ps.set_option(_lib.OPT_TIMING, 0)
         solver.step(args.settled_after)
         ps.sync()
@@ -689,7 +745,7 @@ def main():
     # The spread a reader of the parsed line alone should see: `value` = mean of the preheated blocks;
     # value_single_block = ONE literal "W warm-up + K timed steps" block straight after set-up, no preheat (= cold_block).
     line["value_single_block"] = (cold or first)["value"]
-    if (args.with_bodies and args.workload == "c3p_uniform_1.75M" and args.settle == 0 and not args.ablate_mask
+    if (args.full and args.with_bodies and args.workload == "c3p_uniform_1.75M" and args.settle == 0 and not args.ablate_mask
             and args.gather_impl == 1 and args.fused == 1):
         try:
             line["with_bodies"] = with_bodies(args, local_rank)
@@ -704,7 +760,7 @@ def main():
     line["config"].update(value_is="mean of `reps` preheated W+K blocks from the rest lattice",
                           value_single_block=line["value_single_block"], value_settled=line["value_settled"],
                           value_with_bodies=line["value_with_bodies"])
-    if args.cpu_steps > 0:
+    if args.full and args.cpu_steps > 0:
         line["cpu_baseline"] = cpu_baseline(sd, args.cpu_steps)
     else:
         line["cpu_baseline"] = None

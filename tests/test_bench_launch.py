@@ -197,3 +197,48 @@ def test_bench_ignores_an_inherited_world_size_without_a_launcher():
                        stderr=subprocess.PIPE, timeout=300)
     assert b"WORLD_SIZE=4" not in p.stderr and b"WORLD_SIZE=4" not in p.stdout
     assert b"needs a GPU" in p.stderr or p.returncode == 0
+
+
+def test_dump_outputs_writes_float32_arrays_by_persistent_id_and_samples_above_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: x, v, density, pressure as DIR/<name>.npy in float32, rows in persistent-id order (the
+    same particle in the same row whatever order the cell sort left the arrays in); above the size budget the same fixed,
+    seeded sample of rows in every array, with the ids beside them."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Field:
+        def __init__(self, a):
+            self.a = a
+
+        def to_numpy(self):
+            return self.a.copy()
+
+    class PS:
+        pass
+
+    rng = np.random.default_rng(7)
+    n = 1000
+    pid = rng.permutation(n).astype(np.int32)
+    ps = PS()
+    ps.pid = Field(pid)
+    data = {"x": rng.random((n, 3), dtype=np.float32), "v": rng.random((n, 3), dtype=np.float32),
+            "density": rng.random(n, dtype=np.float32), "pressure": rng.random(n, dtype=np.float32)}
+    for k, a in data.items():
+        setattr(ps, k, Field(a))
+    full = tmp_path / "full"
+    bench.dump_outputs(ps, str(full))
+    assert sorted(os.listdir(full)) == sorted(k + ".npy" for k in data)
+    for k, a in data.items():
+        got = np.load(full / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got[pid], a)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)
+    outs = []
+    for d in ("s1", "s2"):
+        bench.dump_outputs(ps, str(tmp_path / d))
+        outs.append({k: np.load(tmp_path / d / (k + ".npy")) for k in list(data) + ["sample_ids"]})
+    ids = outs[0]["sample_ids"]
+    assert ids.dtype == np.float64 and 0 < len(ids) < n and np.array_equal(ids, outs[1]["sample_ids"])
+    assert sum(a.nbytes for a in outs[0].values()) <= 8000
+    for k in data:
+        assert np.array_equal(outs[0][k], np.load(full / (k + ".npy"))[ids.astype(np.int64)])

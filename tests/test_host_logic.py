@@ -121,14 +121,14 @@ def test_exporters_and_mesh_roundtrip(tmp_path):
     assert np.allclose(m2.vertices, m.vertices) and np.array_equal(m2.faces, m.faces)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/data/scenes"), reason="reference scenes only exist in the build container")
 def test_reference_scene_files_parse_with_expected_counts():
-    """Every scene JSON of the reference parses; fluid particle counts follow particle_system.py:450-456."""
+    """Every scene JSON of the reference parses; fluid particle counts follow particle_system.py:450-456.  The scene
+    files are stored unchanged under tests/golden/reference_data/scenes/."""
     import glob
     from sph_taichi_amd.config_builder import SimConfig
     from sph_taichi_amd import scene as scene_mod
     expect = {"dragon_bath.json": 423500, "armadillo_bath_dynamic.json": 1723968}
-    files = sorted(glob.glob("/root/reference/data/scenes/*.json"))
+    files = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data", "scenes", "*.json")))
     assert len(files) == 7
     for f in files:
         cfg = SimConfig(scene_file_path=f)

@@ -4,12 +4,15 @@
 depth-first subdivision + breadth-first hole filling, its own OBJ reader and quaternion rotation) -- the voxel SETS must be
 identical -- and a geometric classifier that does not know the recipe (exact triangle / cube overlap, ray parity along
 three axes): every sampled voxel's cube touches the surface, every centre inside a closed mesh is filled, whatever else is
-filled is an enclosed exterior pocket (counted).  Runs on generated cubes everywhere and on the reference's own models
-where /root/reference exists (this container); the committed dragon fixture is pinned by hash on both sides."""
+filled is an enclosed exterior pocket (counted).  Runs on generated cubes and on the reference's own models and scene
+files, stored under tests/golden/reference_data/ (Dragon_50k.obj gzip-compressed); the committed dragon fixture is pinned
+by hash on both sides."""
 import glob
+import gzip
 import hashlib
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -22,6 +25,21 @@ REF = "/root/reference"
 PITCH = 0.02
 DRAGON_FIXTURE_SHA256 = "1decd5f51f525490b90eabcf7fe32854a392b9a6a4d71f97fe7ae5e206025af1"
 DRAGON_FIXTURE_ROWS = 18496
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
+
+
+@pytest.fixture(scope="module")
+def ref_root(tmp_path_factory):
+    """A directory laid out like the reference's checkout as far as these tests read it: data/scenes/*.json and the two
+    meshes data/models/{Dragon_50k,bunny_sparse}.obj, restored from tests/golden/reference_data/."""
+    root = tmp_path_factory.mktemp("reference")
+    shutil.copytree(os.path.join(REF_DATA, "scenes"), str(root / "data" / "scenes"))
+    models = root / "data" / "models"
+    models.mkdir()
+    with gzip.open(os.path.join(REF_DATA, "models", "Dragon_50k.obj.gz"), "rb") as f:
+        (models / "Dragon_50k.obj").write_bytes(f.read())
+    shutil.copy(os.path.join(REF_DATA, "models", "bunny_sparse.obj"), str(models / "bunny_sparse.obj"))
+    return str(root)
 
 
 def _closed_mesh_report(body, tmp_note=""):
@@ -90,28 +108,27 @@ needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "data",
                                      reason="/root/reference is not on this machine (the GPU box): the fixture hash test covers it")
 
 
-def _reference_scene_bodies():
+def _reference_scene_bodies(root):
     out = []
-    for path in sorted(glob.glob(os.path.join(REF, "data", "scenes", "*.json"))):
+    for path in sorted(glob.glob(os.path.join(root, "data", "scenes", "*.json"))):
         for body in json.load(open(path)).get("RigidBodies", []):
-            g = os.path.join(REF, body["geometryFile"])
+            g = os.path.join(root, body["geometryFile"])
             if os.path.exists(g):
                 out.append((os.path.basename(path), dict(body, geometryFile=g)))
     return out
 
 
-@needs_reference
-def test_dragon_as_every_reference_scene_places_it():
-    """Every RigidBodies entry of /root/reference/data/scenes/*.json whose mesh exists (Dragon_50k.obj: dragon_bath,
+def test_dragon_as_every_reference_scene_places_it(ref_root):
+    """Every RigidBodies entry of the reference's data/scenes/*.json whose mesh exists (Dragon_50k.obj: dragon_bath,
     dragon_bath_dfsph, dragon_bath_dynamic_dfsph; armadillo_small.obj is missing from the checkout), plus the stand-in the
     C3 workload uses for the armadillo (scale 0.65, half a turn about y).  Dragon_50k.obj: 25,007 vertices, none
     unreferenced, no duplicate position, no boundary edge (16 edges are shared by four faces: two sheets touching), so
     trimesh.load(process=True) keeps the vertex list -- hence the rotation centre -- and repair.fill_holes adds nothing."""
-    audit = vc.mesh_audit(os.path.join(REF, "data/models/Dragon_50k.obj"))
+    audit = vc.mesh_audit(os.path.join(ref_root, "data/models/Dragon_50k.obj"))
     assert audit["unreferenced_vertices"] == 0 and audit["duplicate_positions"] == 0 and audit["boundary_edges"] == 0, audit
-    bodies = _reference_scene_bodies()
+    bodies = _reference_scene_bodies(ref_root)
     assert len(bodies) >= 3
-    bodies.append(("armadillo stand-in", {"geometryFile": os.path.join(REF, "data/models/Dragon_50k.obj"), "scale": [0.65] * 3,
+    bodies.append(("armadillo stand-in", {"geometryFile": os.path.join(ref_root, "data/models/Dragon_50k.obj"), "scale": [0.65] * 3,
                                           "translation": [0.0, 0.0, 0.0], "rotationAxis": [0, 1, 0], "rotationAngle": 180}))
     seen = {}
     for name, body in bodies:
@@ -124,12 +141,11 @@ def test_dragon_as_every_reference_scene_places_it():
         json.dump(seen, open(out, "w"), indent=1)
 
 
-@needs_reference
-def test_open_mesh_is_voxelised_hollow_by_both_and_flagged():
+def test_open_mesh_is_voxelised_hollow_by_both_and_flagged(ref_root):
     """bunny_sparse.obj has 42 boundary edges (the scanner's holes in the base, up to 0.026 long = 5 pitches at scale 4):
     the sampled shell is not closed, hole filling floods the inside, and the body is a hollow shell -- in both
     implementations alike, as trimesh's recipe has it.  The classifier reports the mesh as not closed."""
-    body = {"geometryFile": os.path.join(REF, "data/models/bunny_sparse.obj"), "scale": [4, 4, 4], "translation": [1.0, 0.1, 1.0],
+    body = {"geometryFile": os.path.join(ref_root, "data/models/bunny_sparse.obj"), "scale": [4, 4, 4], "translation": [1.0, 0.1, 1.0],
             "rotationAxis": [1, 1, 0], "rotationAngle": 37}
     assert vc.mesh_audit(body["geometryFile"])["boundary_edges"] == 42
     pts, _ = voxelizer.load_rigid_body(dict(body), PITCH)
@@ -144,14 +160,12 @@ def _fixture_sha():
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def test_committed_dragon_fixture_is_the_checked_voxel_set():
+def test_committed_dragon_fixture_is_the_checked_voxel_set(ref_root):
     """The body every C2 comparison stands on (sph_taichi_amd/data/bodies/dragon_bath_body.npy: 18,496 points, scene
-    translation removed) cannot drift: its bytes are pinned here, and where the reference's mesh is present the SECOND
+    translation removed) cannot drift: its bytes are pinned here, and from the reference's mesh the SECOND
     implementation reproduces it point for point."""
     assert _fixture_sha() == DRAGON_FIXTURE_SHA256
-    if not os.path.isdir(os.path.join(REF, "data", "models")):
-        return
-    body = [b for n, b in _reference_scene_bodies() if n == "dragon_bath.json"][0]
+    body = [b for n, b in _reference_scene_bodies(ref_root) if n == "dragon_bath.json"][0]
     pts = vc.reference(body, PITCH)
     want = np.load(os.path.join(workloads.BODIES, "dragon_bath_body.npy"))
     got = (pts - np.array(body["translation"])).astype(np.float32)

@@ -4,7 +4,7 @@
 #     tests    : pytest -m gpu
 #     pmc      : rocprofv3 PMC passes, from rest and settled -> gpurun_out/<tag>/pmc_traffic.json (+ summaries)
 #     kstats   : rocprofv3 kernel-trace stats of the default bench line's two states
-#     bench    : the default bench line + the other workloads
+#     bench    : the full bench line (--full) + the other workloads
 #     variants : A/B table  partition (adaptive / fixed bricks) x emission (group-sorted / baseline)
 #     native   : kernel trace of the one-rank native RCCL worker + slab driver overhead at world = 1
 #     fastmath : A/B of the fast-math choice (tools/fastmath_ab.py)
@@ -58,14 +58,14 @@ if has kstats; then
   bash tools/gpu_kstats.sh $TAG "--steps 60 --warmup 5 --min-seconds 0 --settled-after 0" "--steps 60 --warmup 5 --settle 2000 --settled-after 0"
 fi
 if has bench; then
-  timeout 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1200 $OUT/bench_default.json; echo
+  timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1200 $OUT/bench_default.json; echo
   timeout 200 python bench.py --steps 20 --warmup 5 --cpu-steps 0 --with-bodies 0 > $OUT/bench_driver_args.json 2>> $OUT/bench.err
   for w in c1_dambreak_262k c2_dragon_bath c3_armadillo_equiv; do
     timeout 200 python bench.py --steps 100 --warmup 10 --cpu-steps 0 --workload $w --settled-after 0 --min-seconds 0 > $OUT/bench_$w.json 2>> $OUT/bench.err
   done
   timeout 200 python bench.py --steps 100 --warmup 10 --cpu-steps 0 --workload c1_dambreak_262k --settle 2500 --settled-after 0 > $OUT/bench_c1_developed.json 2>> $OUT/bench.err
-  timeout 300 python bench.py --steps 30 --warmup 3 --cpu-steps 0 --solver dfsph > $OUT/bench_dfsph_c3p.json 2>> $OUT/bench.err
-  timeout 400 python bench.py --steps 50 --warmup 10 --cpu-steps 0 --workload c4_dambreak --settled-after 2500 --min-seconds 0 --max-reps 1 > $OUT/bench_c4_dambreak_one_gpu.json 2>> $OUT/bench.err
+  timeout 300 python bench.py --full --steps 30 --warmup 3 --cpu-steps 0 --solver dfsph > $OUT/bench_dfsph_c3p.json 2>> $OUT/bench.err
+  timeout 400 python bench.py --full --steps 50 --warmup 10 --cpu-steps 0 --workload c4_dambreak --settled-after 2500 --min-seconds 0 --max-reps 1 > $OUT/bench_c4_dambreak_one_gpu.json 2>> $OUT/bench.err
   for f in driver_args c1_dambreak_262k c2_dragon_bath c3_armadillo_equiv c1_developed dfsph_c3p c4_dambreak_one_gpu; do python -c "import json;d=json.load(open('$OUT/bench_$f.json'));print('$f',d['value'],d['ms_per_step'],d['breakdown_ms'])"; done
 fi
 if has variants; then
@@ -95,6 +95,6 @@ if has timeline; then   # per-workgroup time line of the two brick sweeps (profi
   timeout 600 python tools/brick_timeline.py --out $OUT/brick_timeline.txt > $OUT/brick_timeline.log 2>&1; echo "timeline rc=$?"; grep -v amdgpu $OUT/brick_timeline.log | tail -n 40
 fi
 if has bodies; then     # the default line's with_bodies object alone (C3 with immersed bodies)
-  timeout 300 python bench.py --steps 100 --warmup 10 --cpu-steps 0 --settled-after 0 --min-seconds 0 > $OUT/bench_with_bodies.json 2>> $OUT/bench.err
+  timeout 300 python bench.py --full --steps 100 --warmup 10 --cpu-steps 0 --settled-after 0 --min-seconds 0 > $OUT/bench_with_bodies.json 2>> $OUT/bench.err
   python -c "import json;d=json.load(open('$OUT/bench_with_bodies.json'));print('with_bodies', json.dumps(d.get('with_bodies'))[:900])"
 fi

@@ -51,7 +51,7 @@ def do_run(tags, reps, out, extra):
                 if not os.path.exists(lib_of(tag)):
                     continue
                 env["SPH_HIP_LIB_VARIANT"] = tag
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-steps", "0", "--with-bodies", "0"] + extra,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-steps", "0", "--with-bodies", "0"] + extra,
                                env=env, capture_output=True, text=True, timeout=400)
             try:
                 d = json.loads(r.stdout.strip().splitlines()[-1])
