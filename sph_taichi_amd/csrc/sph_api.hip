@@ -91,6 +91,9 @@ int sph_check_device_flags(SphContext* c) {
     return 0;
 }
 
+// SPH_OPT_KERNEL_VARIANT / the SPH_KERNEL_VARIANT environment default: GAT_LDS and GAT_LDS4 exclude each other
+static bool variant_mask_ok(int v) { return (v & (SPH_VAR_GAT_LDS | SPH_VAR_GAT_LDS4)) != (SPH_VAR_GAT_LDS | SPH_VAR_GAT_LDS4); }
+
 extern "C" {
 
 int32_t sph_abi_version(void) { return SPH_ABI_VERSION; }
@@ -149,7 +152,6 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     c->opt_rigid_batch = 1;
     c->opt_df_fuse_err = 1;
     c->df_collect = 0;
-    c->df_bpart_valid = false;
     c->opt_df_runahead = 0;   // measured (r05): running ahead costs 2 % more than the bubbles it removes
     c->opt_exact_math = 0;
     c->opt_rigid_x0 = 0;
@@ -247,7 +249,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     sph_invalidate_lists(c);
     c->opt_uniform = -1; c->uniform_state = -1; c->m_uniform = 0.0f;  // SPH_OPT_UNIFORM_FLUID: auto
     c->opt_variant = SPH_VAR_DEFAULT;
-    if (const char* e = getenv("SPH_KERNEL_VARIANT")) c->opt_variant = atoi(e) & 31;  // A/B aid: the default mask of every context of this process
+    if (const char* e = getenv("SPH_KERNEL_VARIANT")) { const int v = atoi(e) & 31; c->opt_variant = variant_mask_ok(v) ? v : SPH_VAR_DEFAULT; }  // A/B aid: the default mask of every context of this process
     memset(&c->df_stats, 0, sizeof(c->df_stats));
     c->df.enable_divergence_solver = 1; c->df.m_max_iterations_v = 100; c->df.m_max_iterations = 100;  // DFSPH.py:12-20
     c->df.fluid_particle_num = 0; c->df.m_eps = 1e-5f; c->df.reserved_ = 0.0f; c->df.max_error_V = 0.1; c->df.max_error = 0.05;
@@ -299,7 +301,7 @@ int32_t sph_set_option(SphContext* c, int32_t option, int32_t value) {
         case SPH_OPT_EXACT_MATH: c->opt_exact_math = value ? 1 : 0; sph_invalidate_lists(c); return 0;
         case SPH_OPT_DF_RUNAHEAD: c->opt_df_runahead = value ? 1 : 0; return 0;
         case SPH_OPT_KERNEL_VARIANT:
-            if (value < -1 || value > 63 || (value > 0 && (value & 6) == 6)) return sph_fail(c, SPH_E_INVALID, "kernel variant must be -1 (default) or a mask of SPH_VAR_* (GAT_LDS and GAT_LDS4 exclude each other)");
+            if (value < -1 || value > 63 || (value > 0 && !variant_mask_ok(value))) return sph_fail(c, SPH_E_INVALID, "kernel variant must be -1 (default) or a mask of SPH_VAR_* (GAT_LDS and GAT_LDS4 exclude each other)");
             c->opt_variant = value < 0 ? SPH_VAR_DEFAULT : value;
             sph_invalidate_lists(c);
             return 0;
@@ -364,8 +366,7 @@ int32_t sph_set_particle_count(SphContext* c, int32_t n) {
     c->N = n;
     c->n_dyn_host = -1;
     sph_forget_pure_fluid(c);
-    sph_invalidate_lists(c);
-    c->aux_stale = false;
+    sphd_set_changed(c->dv);
     c->have_keys = c->have_prefix = false;
     return 0;
 }
@@ -637,7 +638,7 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
         // stg / gat copies), so each fluid target is integrated right in the sweep's finish and the streaming advect
         // kernel disappears.  Dynamic rigid particles collect coupling reactions from many workgroups during the sweep:
         // they are integrated afterwards, by a kernel over their (short) list.
-        const bool fuse = c->uniform_state == 1 && c->stg_kind == 1 && c->lists_valid && !c->opt_drop_outside &&
+        const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && !c->opt_drop_outside &&
                           c->opt_gather_impl == 1 && c->N > 0;
         c->fuse_advect = fuse ? 1 : 0;
         rc = sphk_gather(c, GM_FORCE_FUSED);                // WCSPH.py:154-155 (+ :156 and sph_base.py:270-271 when fused)
@@ -843,8 +844,7 @@ int32_t sph_select_range(SphContext* c, int32_t first, int32_t count) {
     c->in_off += first;
     c->N = count;
     sph_forget_pure_fluid(c);
-    sph_invalidate_lists(c);
-    c->aux_stale = false;  // (eos2 is indexed from the old first record)
+    sphd_set_changed(c->dv);
     c->have_keys = c->have_prefix = c->sorted = false;
     c->n_dyn_host = -1;
     return 0;
@@ -1015,7 +1015,7 @@ int32_t sph_slab_forces(SphContext* c, int32_t bl_lo, int32_t bl_hi, int32_t br_
     // interior: overlaps with the exchange; with the one-gather sweep its finish integrates its own targets (see
     // step_sweeps), so that afterwards only the two boundary ranges -- exactly the packed ranges -- are left to advect
     // (ghost records are not advected at all: the exchange replaces them)
-    const bool fuse = c->uniform_state == 1 && c->stg_kind == 1 && c->lists_valid && c->opt_no_dynamic;
+    const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && c->opt_no_dynamic;
     c->fuse_advect = fuse ? 1 : 0;
     // (an interior target's acceleration is consumed by the advect in the same finish and by nobody else -- the packers
     // read the BOUNDARY sets' -- so, as inside sph_step, it is not written out: 16 B per particle and step less)
@@ -1176,7 +1176,7 @@ static int df_enqueue_body(SphContext* c, const DfSolve& s, int k) {
     int rc = sphk_gather(c, s.sweep);                    // *_solver_iteration(): kernel,
     // (the refresh sweep also reduces the density error over its own targets, brick by brick, when it runs as a brick sweep)
     c->df_collect = c->opt_df_fuse_err;
-    c->df_bpart_valid = false;
+    sphd_bpart_consumed(c->dv);
     rc = rc ? rc : sphk_gather(c, s.refresh);            //   compute_density_change() / compute_density_adv(),
     c->df_collect = 0;
     rc = rc ? rc : sphk_df_convergence_test(c, s.offset, s.eta, k & 3);  // compute_density_error() + the test

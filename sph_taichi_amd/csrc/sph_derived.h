@@ -1,0 +1,100 @@
+// sph_derived.h -- which derived device buffers still describe the current particle state.
+//
+// Host only, no HIP: tests/derived_state_driver.cpp runs the rules below on the CPU.  The fields of SphDerived are
+// touched by the functions of this header and by nobody else; the launch code reports EVENTS and asks QUESTIONS.
+//
+// The rules:
+//   * The neighbour lists (glist / gcnt) hold offsets into the tile of the brick that wrote them, so they belong to the
+//     partition (brick_list) they were written over.  Whatever replaces the cached partition drops the lists, and the
+//     column records (brick_rec) and staging records with them.
+//   * The column records serve only a reader whose target ranges are exactly the writer's (a subset sweep -- slab
+//     mode -- has other target tables); the lists serve every reader the cached partition serves.
+//   * What survives sphd_invalidate(), on purpose:
+//       gcnt_written      sph_get_stats after a step reports the last density sweep's list lengths although the advect
+//                         has moved the particles since; only a sort (which reorders gcnt's index space) ends that.
+//       aux_stale         density / pressure in eos2 stay the values of their particles when positions or options
+//                         change; a sort or a new record selection (other indices) ends that.
+//       df_bpart_valid    set and consumed inside one solver iteration, with nothing in between.
+//       brick_count_zero  describes the counter, not the particles.
+#pragma once
+
+// identity of a brick partition: the cut rule and the target x-layer ranges it was cut for
+struct SphPartKey {
+    int id;                // footprint, cut rule, limits
+    int lo, hi, lo2, hi2;  // target layers [lo, hi) u [lo2, hi2)
+    bool operator==(const SphPartKey& o) const { return id == o.id && lo == o.lo && hi == o.hi && lo2 == o.lo2 && hi2 == o.hi2; }
+    // both ranges lie inside the SINGLE range of `o`: bricks listed for `o` that hold no target of ours leave at T == 0
+    bool inside(const SphPartKey& o) const {
+        const bool in1 = lo >= o.lo && hi <= o.hi;
+        const bool in2 = lo2 == hi2 || (lo2 >= o.lo && hi2 <= o.hi);
+        return id == o.id && o.lo2 == o.hi2 && in1 && in2;
+    }
+};
+
+enum SphPartHit { SPH_PART_NO = 0, SPH_PART_SUBSET = 1, SPH_PART_EXACT = 2 };
+
+struct SphDerived {
+    bool lists_valid;       // glist / gcnt describe the current positions and order, over the cached partition
+    bool gcnt_written;      // gcnt was written by a brick density sweep since the last sort
+    int stg_kind;           // what stg / gat hold for the current positions: 0 nothing, 1 the WCSPH records of
+                            // GM_DENSITY_EOS, 2 the DFSPH record (x, y, z, +m_V fluid / -m_V solid) of GM_DF_DENSITY
+    int k_kind;             // gat-as-float holds k_j = b_j * factor_j: 0 no, 1 b = density_adv, 2 b = density_adv - 1
+    bool bricks_valid;      // brick_list / brick_count describe the current order for bricks_key
+    SphPartKey bricks_key;
+    bool brec_valid;        // brick_rec describes the current lists for a reader of brec_key
+    SphPartKey brec_key;
+    bool df_bpart_valid;    // the refresh sweep of this solver iteration left its per-brick density-error partials
+    bool aux_stale;         // density / pressure of the fluid live in eos2 (lean density finish), not yet in aux
+    bool brick_count_zero;  // brick_count is zero (hash kernel) and no list has been built into it since
+};
+
+// ---- events ----------------------------------------------------------------------------------------------------------
+// positions, flags, the particle set or an option the sweeps' instances depend on changed; also the scan's error flag
+static inline void sphd_invalidate(SphDerived& s) { s.lists_valid = s.bricks_valid = s.brec_valid = false; s.stg_kind = s.k_kind = 0; }
+// ... and the records were re-based (sph_set_particle_count, sph_select_range): eos2 is indexed from the old first record
+static inline void sphd_set_changed(SphDerived& s) { sphd_invalidate(s); s.aux_stale = false; }
+// a sort has been enqueued; `built`: its place kernel cut the step's partition under `key` (into the zeroed counter)
+static inline void sphd_sorted(SphDerived& s, bool built, const SphPartKey& key) {
+    sphd_set_changed(s);  // (eos2 is in the old order: whoever needed density / pressure called sph_ensure_aux before)
+    s.gcnt_written = false;
+    s.brick_count_zero = false;
+    s.bricks_valid = built;
+    if (built) s.bricks_key = key;
+}
+// a sweep cut a partition of its own into the main stream's list: the lists of the old one cannot be read through it
+static inline void sphd_partition_rebuilt(SphDerived& s, const SphPartKey& key) {
+    s.lists_valid = s.brec_valid = false;
+    s.brick_count_zero = false;
+    s.bricks_valid = true;
+    s.bricks_key = key;
+}
+// a list-writing sweep ran; stg_kind = the staging records it left (1 comes with density / pressure in eos2 only)
+static inline void sphd_lists_written(SphDerived& s, int stg_kind) {
+    s.lists_valid = s.gcnt_written = true;
+    s.stg_kind = stg_kind;
+    s.k_kind = 0;
+    if (stg_kind == 1) s.aux_stale = true;
+}
+// ... and left its column records, for readers of exactly `key` (stream order: every later sweep runs behind it)
+static inline void sphd_records_written(SphDerived& s, const SphPartKey& key) { s.brec_valid = true; s.brec_key = key; }
+// k_j written by a density-change (1) / density-advection (2) sweep, or stale (0: the cell walk, sphk_df_scale_factor)
+static inline void sphd_k_written(SphDerived& s, int kind) { s.k_kind = kind; }
+static inline void sphd_bpart_written(SphDerived& s) { s.df_bpart_valid = true; }
+static inline void sphd_bpart_consumed(SphDerived& s) { s.df_bpart_valid = false; }
+static inline void sphd_aux_folded(SphDerived& s) { s.aux_stale = false; }
+static inline void sphd_count_zeroed(SphDerived& s, bool zero) { s.brick_count_zero = zero; }
+
+// ---- questions -------------------------------------------------------------------------------------------------------
+static inline SphPartHit sphd_partition_hit(const SphDerived& s, const SphPartKey& key) {
+    if (!s.bricks_valid) return SPH_PART_NO;
+    return key == s.bricks_key ? SPH_PART_EXACT : key.inside(s.bricks_key) ? SPH_PART_SUBSET : SPH_PART_NO;
+}
+static inline bool sphd_lists_usable(const SphDerived& s) { return s.lists_valid; }
+static inline bool sphd_records_usable(const SphDerived& s, const SphPartKey& key) { return s.lists_valid && s.brec_valid && key == s.brec_key; }
+// the one-gather sweeps: lists current and the staging records of the right kind (DFSPH: and k_j of the right kind)
+static inline bool sphd_one_gather_wcsph(const SphDerived& s) { return s.lists_valid && s.stg_kind == 1; }
+static inline bool sphd_one_gather_df(const SphDerived& s, int k_kind) { return s.lists_valid && s.stg_kind == 2 && s.k_kind == k_kind; }
+static inline bool sphd_stats_have_lists(const SphDerived& s) { return s.gcnt_written; }
+static inline bool sphd_bpart_ready(const SphDerived& s) { return s.df_bpart_valid; }
+static inline bool sphd_aux_in_eos2(const SphDerived& s) { return s.aux_stale; }
+static inline bool sphd_count_is_zero(const SphDerived& s) { return s.brick_count_zero; }

@@ -913,6 +913,7 @@ __global__ __launch_bounds__(TPB, (brick_waves_per_simd<MODE, VAR>())) void k_ga
 
     // ---- step A: per shell column, the cell-end table and the segment scan (wave 0) ----
     if (from_rec) {
+        static_assert((CFG::BX + 2) * (CFG::BY + 2) < 32, "a column record has 32 rows: the shell columns and at least one row of totals");
         if (tid < 32) {   // (lanes >= the brick's column count hold the totals, like the tables they stand for)
             const int4 r = brec[(size_t)bidx * 32 + tid];
             sColG[tid] = r.x; sColS[tid] = r.y; sTG[tid] = r.z; sTOff[tid] = r.w;
@@ -1573,8 +1574,8 @@ __global__ __launch_bounds__(TPB) void k_aux_from_eos2(DevView d) {
 }
 
 int sph_ensure_aux(SphContext* c) {
-    if (!c->aux_stale) return 0;
-    c->aux_stale = false;
+    if (!sphd_aux_in_eos2(c->dv)) return 0;
+    sphd_aux_folded(c->dv);
     if (c->N <= 0) return 0;
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_aux_from_eos2, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d);
@@ -1629,12 +1630,14 @@ static int brick_partition_id(const SphContext* c) {
     const int fixed_bz = c->opt_brick_shape == 1 ? SPH_BRICK_BZ : 0;
     return ((SPH_BRICK_BX * 10 + SPH_BRICK_BY) * 10 + SPH_BRICK_BZ) * 4096 + fixed_bz * 2048 + brick_smax(c);
 }
+static SphPartKey brick_key(const SphContext* c, const DevView& d) { return {brick_partition_id(c), d.tgt_lo, d.tgt_hi, d.tgt_lo2, d.tgt_hi2}; }
 
 // The list for the step's default sweeps (targets = the density layers), to be built by the sort's place kernel in
-// extra workgroups: fills `a` (nblocks = 0 if the brick sweeps will not run) and records the key; the caller marks the
-// cache valid once the sort has been enqueued.
-int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a) {
+// extra workgroups: fills `a` (nblocks = 0 if the brick sweeps will not run) and `key`; the caller reports both once the
+// sort has been enqueued.
+int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a, SphPartKey* key) {
     memset(a, 0, sizeof(*a));
+    *key = SphPartKey{};
     if (c->N <= 0 || c->opt_gather_impl != 1 || !brick_ok(c)) return 0;
     DevView d = sph_view(c);
     d.tgt_lo = c->tgt_layers[0]; d.tgt_hi = c->tgt_layers[1]; d.tgt_lo2 = d.tgt_hi2 = 0;
@@ -1649,8 +1652,7 @@ int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a) {
     a->tmax = TPB; a->smax = brick_smax(c); a->fixed_bz = c->opt_brick_shape == 1 ? SPH_BRICK_BZ : 0;
     a->nblocks = (nbx * nby + TPB / 64 - 1) / (TPB / 64);
     a->lds_bytes = (unsigned)((TPB / 64) * 5 * (d.nz + 1) * sizeof(int));
-    const int key[5] = {brick_partition_id(c), d.tgt_lo, d.tgt_hi, 0, 0};
-    memcpy(c->bricks_key, key, sizeof(key));
+    *key = brick_key(c, d);
     return 0;
 }
 
@@ -1684,7 +1686,7 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
     // another wrote (list entries are brick-relative).
     const int fixed_bz = c->opt_brick_shape == 1 ? CFG::BZ : 0;
     const int tmax = TPB, smax = brick_smax(c);
-    const int key[5] = {brick_partition_id(c), d.tgt_lo, d.tgt_hi, d.tgt_lo2, d.tgt_hi2};
+    const SphPartKey key = brick_key(c, d);
     hipStream_t st = sph_stream(c);
     int2* blist = c->use_side ? c->brick_list2 : c->brick_list;
     int* bcount = c->use_side ? c->brick_count2 : c->brick_count;
@@ -1693,24 +1695,18 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
     // layers. Bricks listed for the wider range that hold no target of this sweep leave at T == 0. For a sweep that
     // reads the neighbour lists this is not an economy but the rule: the entries are offsets into the tile of the brick
     // that wrote them, and the adaptive cut depends on the target ranges, so a partition of its own would misread them.
-    const bool in1 = key[1] >= c->bricks_key[1] && key[2] <= c->bricks_key[2];
-    const bool in2 = key[3] == key[4] || (key[3] >= c->bricks_key[1] && key[4] <= c->bricks_key[2]);
-    const bool subset = c->bricks_valid && key[0] == c->bricks_key[0] && c->bricks_key[3] == c->bricks_key[4] && in1 && in2;
-    const bool cached = c->bricks_valid && (memcmp(key, c->bricks_key, sizeof(key)) == 0 || subset);
-    if (cached) {
+    if (sphd_partition_hit(c->dv, key) != SPH_PART_NO) {
         blist = c->brick_list; bcount = c->brick_count;  // (read-only here; the side stream forked after it was built)
     } else {
         if (mode_reads_list<MODE>())
             return sph_fail(c, SPH_E_INVALID, "the sweep reads neighbour lists but its targets lie outside the partition that wrote them");
-        if (c->use_side || !c->brick_count_zero) SPH_HIP(c, hipMemsetAsync(bcount, 0, 2 * sizeof(int), st));
-        if (!c->use_side) c->brick_count_zero = false;
+        if (c->use_side || !sphd_count_is_zero(c->dv)) SPH_HIP(c, hipMemsetAsync(bcount, 0, 2 * sizeof(int), st));
         hipLaunchKernelGGL((k_brick_list<CFG>), dim3((ncg + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), (size_t)(TPB / 64) * 5 * (d.nz + 1) * sizeof(int),
                            st, d, nbx, nby, blist, bcount, c->brick_cap, tmax, smax, fixed_bz);
         SPH_LAUNCH_CHECK(c);
-        if (!c->use_side) {  // (the side stream's list is private to that launch and never cached)
-            memcpy(c->bricks_key, key, sizeof(key));
-            c->bricks_valid = true;
-        }
+        // (the side stream's list is private to that launch and never cached)  The main stream's replaces the cached one, and
+        // the lists and column records written over that one go with it: their entries are relative to ITS bricks.
+        if (!c->use_side) sphd_partition_rebuilt(c->dv, key);
     }
     // the per-brick column records: written by a list-writing sweep over the cached list of the main stream, read back by
     // the list readers whose target ranges are exactly the writer's (a subset sweep -- slab mode -- has other target tables)
@@ -1719,9 +1715,8 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
     if (c->brick_rec && blist == c->brick_list && c->opt_brick_rec) {
         if (mode_writes_list<MODE>()) {
             brec = c->brick_rec;
-            memcpy(c->brec_key, key, sizeof(key));
-            c->brec_valid = true;     // (stream order: every later sweep runs behind this launch)
-        } else if (mode_reads_list<MODE>() && c->brec_valid && memcmp(key, c->brec_key, sizeof(key)) == 0) {
+            sphd_records_written(c->dv, key);
+        } else if (mode_reads_list<MODE>() && sphd_records_usable(c->dv, key)) {
             brec = c->brick_rec;
             use_rec = 1;
         }
@@ -1764,6 +1759,18 @@ static int launch_brick(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0, in
     return launch_brick_cfg<MODE, Cfg0>(c, lo, hi, lo2, hi2);
 }
 
+// what a brick sweep that was enqueued without error leaves behind (sph_derived.h)
+template <int MODE>
+static int sweep_done(SphContext* c, int rc) {
+    if (rc) return rc;
+    if (MODE == GM_DENSITY_EOS) sphd_lists_written(c->dv, c->uniform_state == 1 ? 1 : 0);
+    if (MODE == GM_DF_DENSITY) sphd_lists_written(c->dv, 2);
+    if (mode_is_df_vdiv<MODE>() && c->df_collect) sphd_bpart_written(c->dv);  // every listed brick leaves its partial of the density error
+    if (MODE == GM_DF_DENSITY_CHANGE) sphd_k_written(c->dv, 1);
+    if (MODE == GM_DF_DENSITY_ADV) sphd_k_written(c->dv, 2);
+    return 0;
+}
+
 // force sweep over the targets of x layers [lo, hi) only (slab mode: boundary layers first, interior later)
 int sphk_gather_layers(SphContext* c, int mode, int lo, int hi, int lo2, int hi2) {
     if (c->N <= 0 || (hi <= lo && hi2 <= lo2)) return 0;
@@ -1772,18 +1779,15 @@ int sphk_gather_layers(SphContext* c, int mode, int lo, int hi, int lo2, int hi2
                                           "or more than 1000 cell layers in z): cut the domain into more slabs");
     if (mode != GM_FORCE_FUSED || c->opt_gather_impl == 0) return sph_fail(c, SPH_E_INVALID, "layer-restricted sweeps need the brick force kernel");
     if (hi < lo) hi = lo;
-    if (c->uniform_state == 1 && c->lists_valid && c->stg_kind == 1) return launch_brick<GM_FORCE_FUSED_U>(c, lo, hi, lo2, hi2);
-    return launch_brick<GM_FORCE_FUSED>(c, lo, hi, lo2, hi2);
+    if (c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, launch_brick<GM_FORCE_FUSED_U>(c, lo, hi, lo2, hi2));
+    return sweep_done<GM_FORCE_FUSED>(c, launch_brick<GM_FORCE_FUSED>(c, lo, hi, lo2, hi2));
 }
 
 template <int MODE>
 static int launch_sweep(SphContext* c) {
     if (c->N <= 0) return 0;
     if (c->opt_gather_impl == 0 || !brick_ok(c)) return launch_simple<MODE>(c, nullptr, c->N);
-    int rc = launch_brick<MODE>(c);
-    if (!rc && mode_writes_list<MODE>()) { c->lists_valid = true; c->gcnt_written = true; }
-    if (!rc && MODE == GM_DENSITY_EOS) { c->stg_kind = c->uniform_state == 1 ? 1 : 0; if (c->stg_kind == 1) c->aux_stale = true; }
-    return rc;
+    return sweep_done<MODE>(c, launch_brick<MODE>(c));
 }
 
 // DFSPH sweeps: one brick shape (the lists of GM_DF_DENSITY are read back by every later sweep of the step, so
@@ -1792,8 +1796,8 @@ static int launch_sweep(SphContext* c) {
 template <int MODE>
 static int launch_df(SphContext* c) {
     if (c->N <= 0) return 0;
-    if (c->opt_gather_impl == 0 || !brick_ok(c) || (mode_reads_list<MODE>() && !c->lists_valid)) {
-        if (mode_is_df_vdiv<MODE>()) c->k_kind = 0;  // density_adv changes, the walk does not refresh k_j
+    if (c->opt_gather_impl == 0 || !brick_ok(c) || (mode_reads_list<MODE>() && !sphd_lists_usable(c->dv))) {
+        if (mode_is_df_vdiv<MODE>()) sphd_k_written(c->dv, 0);  // density_adv changes, the walk does not refresh k_j
         return launch_simple<MODE>(c, nullptr, c->N);
     }
     // (the group-sorted emission and the early entry loads of SPH_VAR_DEEP do nothing measurable for these sweeps: DFSPH
@@ -1801,17 +1805,10 @@ static int launch_df(SphContext* c) {
     // (round 6) ... but the list-WRITING sweep of the step is the same filter + emission as the WCSPH density sweep, and the
     // group-sorted emission is worth as much to it: 0.333 -> 0.24 ms on the settled 1.75 M box (tools/list_reuse_probe.py had
     // timed it at the baseline emission's 0.333 against the WCSPH sweep's 0.245)
-    int rc;
     if constexpr (MODE == GM_DF_DENSITY) {
-        rc = (c->opt_variant & SPH_VAR_GROUPS) ? launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c) : launch_brick_cfg<MODE, Cfg0>(c);
-    } else {
-        rc = launch_brick_cfg<MODE, Cfg0>(c);
+        if (c->opt_variant & SPH_VAR_GROUPS) return sweep_done<MODE>(c, launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c));
     }
-    if (!rc && mode_writes_list<MODE>()) { c->lists_valid = true; c->gcnt_written = true; c->stg_kind = 2; c->k_kind = 0; }
-    if (!rc && mode_is_df_vdiv<MODE>() && c->df_collect) c->df_bpart_valid = true;   // every listed brick leaves its partial of the density error
-    if (!rc && MODE == GM_DF_DENSITY_CHANGE) c->k_kind = 1;
-    if (!rc && MODE == GM_DF_DENSITY_ADV) c->k_kind = 2;
-    return rc;
+    return sweep_done<MODE>(c, launch_brick_cfg<MODE, Cfg0>(c));
 }
 
 static int gather_dispatch(SphContext* c, int mode);
@@ -1826,7 +1823,7 @@ int sphk_gather(SphContext* c, int mode) {
 
 static int gather_dispatch(SphContext* c, int mode) {
     // every sweep but the fused step's own pair reads or rewrites density / pressure in aux
-    if (c->aux_stale && mode != GM_DENSITY_EOS && mode != GM_FORCE_FUSED && mode != GM_BVOL_STATIC && mode != GM_BVOL_DYNAMIC) {
+    if (sphd_aux_in_eos2(c->dv) && mode != GM_DENSITY_EOS && mode != GM_FORCE_FUSED && mode != GM_BVOL_STATIC && mode != GM_BVOL_DYNAMIC) {
         int rc = sph_ensure_aux(c);
         if (rc) return rc;
     }
@@ -1847,8 +1844,8 @@ static int gather_dispatch(SphContext* c, int mode) {
         case GM_FORCE_FUSED:
             // one gather per pair when every fluid particle has the same mass (and the density sweep of this step
             // left its stg / gat records): see SPH_OPT_UNIFORM_FLUID
-            if (c->uniform_state == 1 && c->opt_gather_impl == 1 && brick_ok(c) && c->lists_valid && c->stg_kind == 1 && c->N > 0)
-                return launch_brick<GM_FORCE_FUSED_U>(c);
+            if (c->uniform_state == 1 && c->opt_gather_impl == 1 && brick_ok(c) && sphd_one_gather_wcsph(c->dv) && c->N > 0)
+                return sweep_done<GM_FORCE_FUSED_U>(c, launch_brick<GM_FORCE_FUSED_U>(c));
             return launch_sweep<GM_FORCE_FUSED>(c);
         case GM_DF_DENSITY: return launch_df<GM_DF_DENSITY>(c);
         case GM_DF_FACTOR: return launch_df<GM_DF_FACTOR>(c);
@@ -1857,10 +1854,10 @@ static int gather_dispatch(SphContext* c, int mode) {
         // Jacobi sweeps: with the lists, the sign-coded staging records and k_j = b_j * factor_j all current (the
         // solver loops inside the library keep them so), the neighbour costs one 4-byte gather instead of two records
         case GM_DF_DIV_ITER:
-            if (c->opt_gather_impl == 1 && c->lists_valid && c->stg_kind == 2 && c->k_kind == 1) return launch_df<GM_DF_DIV_ITER_U>(c);
+            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 1)) return launch_df<GM_DF_DIV_ITER_U>(c);
             return launch_df<GM_DF_DIV_ITER>(c);
         case GM_DF_PRESSURE_ITER:
-            if (c->opt_gather_impl == 1 && c->lists_valid && c->stg_kind == 2 && c->k_kind == 2) return launch_df<GM_DF_PRESSURE_ITER_U>(c);
+            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 2)) return launch_df<GM_DF_PRESSURE_ITER_U>(c);
             return launch_df<GM_DF_PRESSURE_ITER>(c);
         case GM_DF_NONPRESSURE: return launch_df<GM_DF_NONPRESSURE>(c);
     }
@@ -1955,7 +1952,7 @@ int sphk_stats(SphContext* c, SphStats* out) {
     unsigned long long h[7];
     // (list lengths only if a brick density sweep wrote gcnt for the current order: ADVICE r02 -- otherwise the
     // fields stay 0 instead of showing stale or never-written bytes)
-    hipLaunchKernelGGL(k_stats, dim3(nb), dim3(TPB), 0, c->stream, d, c->gcnt_written ? c->gcnt : nullptr, part);
+    hipLaunchKernelGGL(k_stats, dim3(nb), dim3(TPB), 0, c->stream, d, sphd_stats_have_lists(c->dv) ? c->gcnt : nullptr, part);
     SPH_LAUNCH_CHECK(c);
     hipLaunchKernelGGL(k_stats_total, dim3(1), dim3(TPB), 0, c->stream, part, nb, dev);
     SPH_LAUNCH_CHECK(c);

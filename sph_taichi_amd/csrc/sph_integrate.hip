@@ -1156,7 +1156,7 @@ int sphk_df_scale_factor(SphContext* c, float s) {
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_df_scale_factor, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, s);
     SPH_LAUNCH_CHECK(c);
-    c->k_kind = 0;  // k_j = b_j * factor_j is stale now
+    sphd_k_written(c->dv, 0);  // k_j = b_j * factor_j is stale now
     return 0;
 }
 
@@ -1184,8 +1184,8 @@ int sphk_df_convergence_test(SphContext* c, float offset, double eta, int slot) 
     SphContext::DfSlot* dev_slot = nullptr;
     SPH_HIP(c, hipHostGetDevicePointer((void**)&dev_slot, c->h_df_slot, 0));
     const int count = c->df.fluid_particle_num > 0 ? c->df.fluid_particle_num : 1;
-    if (c->df_bpart_valid) {   // the refresh sweep ran as a brick sweep and left one partial per listed brick (SPH_OPT_DF_FUSE_ERROR)
-        c->df_bpart_valid = false;
+    if (sphd_bpart_ready(c->dv)) {   // the refresh sweep ran as a brick sweep and left one partial per listed brick (SPH_OPT_DF_FUSE_ERROR)
+        sphd_bpart_consumed(c->dv);
         hipLaunchKernelGGL(k_df_convergence_test_bricks, dim3(1), dim3(1024), 0, c->stream, c->df_bpart, c->brick_count, c->brick_cap, count,
                            eta, dev_slot + slot, c->df_gate, c->df_epoch);
         SPH_LAUNCH_CHECK(c);

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/sph_hip.h"
+#include "sph_derived.h"
 
 #define SPH_MATERIAL_SOLID 0  // particle_system.py:30
 #define SPH_MATERIAL_FLUID 1  // particle_system.py:31
@@ -122,7 +123,6 @@ struct SphContext {
     int* cell_end;     // [G+1] the CURRENT cell array (one of cell_buf[])
     int* cell_buf[2];  // two cell arrays: while one serves the sweeps, the scatter zeroes the other for the next histogram
     int cell_cur;
-    bool brick_count_zero;  // brick_count is zero (set by the hash kernel) and no list has been built into it since
     bool next_cells_zero;  // cell_buf[cell_cur ^ 1] is all zero (no memset needed before the next histogram)
     int* rank_off;     // [cap] arbitrary intra-cell offset from the histogram atomics
     int* idx_unstable; // [cap]
@@ -135,8 +135,6 @@ struct SphContext {
     unsigned char* gcnt;    // [cap] list lengths (255 = take the global cell walk)
     int4* brick_rec;        // [brick_cap][32] per-brick column tables (LDS slot -> global, segment start, target start, target offset) left by
                             // the list-writing sweep for the readers of its lists (k_gather_brick step A); null: not allocated
-    bool brec_valid;        // brick_rec describes the current lists for the partition / target ranges in brec_key
-    int brec_key[5];
     int opt_brick_rec;      // SPH_OPT_BRICK_RECORDS (default 1)
     int2* brick_list;       // [brick_cap] bricks of the sweep being launched: (column group, first z layer | height << 16)
     int* brick_count;       // device counter
@@ -155,13 +153,7 @@ struct SphContext {
     void* stage;       // upload/download staging, cap*16 bytes (>= G*4)
     size_t stage_bytes;
     bool have_keys, have_prefix, sorted;
-    bool lists_valid;   // glist/gcnt describe the CURRENT positions and order (written by a list-writing brick sweep)
-    bool gcnt_written;  // gcnt was written by a brick density sweep since the last sort (sph_get_stats reports list lengths only then)
-    int stg_kind;       // what stg / gat hold for the current positions: 0 nothing, 1 the WCSPH records of
-                        // GM_DENSITY_EOS, 2 the DFSPH record (x, y, z, +m_V fluid / -m_V solid) of GM_DF_DENSITY
-    int k_kind;         // gat-as-float holds k_j = b_j * factor_j: 0 no, 1 b = density_adv, 2 b = density_adv - 1
-    bool bricks_valid;  // brick_list/brick_count describe the current order for the target ranges in bricks_key
-    int bricks_key[5];  // partition id (footprint, cut rule, limits), tgt_lo, tgt_hi, tgt_lo2, tgt_hi2
+    SphDerived dv;      // which derived buffers (lists, partition, column records, staging, k_j, ...) are current: sph_derived.h
     double* h_df_err;   // pinned, device-visible: result of compute_density_error
     struct DfSlot { float err; int converged; double avg; }* h_df_slot;  // [4] pinned, device-visible: the convergence test of a solver iteration
     unsigned* df_gate;  // device word: epoch of the last solve that converged (DevView::gate)
@@ -171,7 +163,6 @@ struct SphContext {
     double* df_part;    // [SPH_DF_ERR_BLOCKS] per-workgroup partial sums
     double* df_bpart;   // [brick_cap] per-BRICK partial sums of the density error, written by the refresh sweep of a solver iteration (SPH_OPT_DF_FUSE_ERROR)
     int df_collect;     // the sweep being enqueued is such a refresh sweep (sph_view hands df_bpart to the kernel)
-    bool df_bpart_valid;  // ... and it went through the brick kernel: the convergence test adds up df_bpart instead of re-reading the particles
     int opt_df_fuse_err;  // SPH_OPT_DF_FUSE_ERROR (default 1)
     SphDfsphParams df;  // DFSPH solver knobs
     SphDfsphStats df_stats;
@@ -190,8 +181,6 @@ struct SphContext {
     int skip_acc;        // set by sph_step for every step but the last of a call: the fused force finish keeps its acceleration to itself
     bool acc_partial;    // sph_slab_forces with the interior advect fused: the interior targets' accelerations were consumed in the
                          // force finish and never written out; sph_download(ACCELERATION) refuses until something writes them all
-    bool aux_stale;      // density / pressure of the fluid live in eos2 (written by the lean density finish), not yet in aux:
-                         // sph_ensure_aux folds them in before anything reads aux.y / aux.z or a reference-API sort moves the records
     int opt_uniform;     // SPH_OPT_UNIFORM_FLUID: -1 auto, 0 off, 1 check once
     int uniform_state;   // -1 unknown, 0 the precondition fails, 1 holds (m_uniform valid)
     int pure_fluid;      // (with uniform_state == 1) the check found no solid particle at all among pure_fluid_n particles:
@@ -207,9 +196,9 @@ struct SphContext {
 
 DevView sph_view(const SphContext* c);
 static inline hipStream_t sph_stream(const SphContext* c) { return c->use_side ? c->side : c->stream; }
-// particle positions / order / flags changed: neighbour lists and the non-empty-brick list are stale
 #define SPH_BRICK_HEAVY 160  // targets from which a brick counts as heavy (a full 4x2x4 brick at rest has 256)
-static inline void sph_invalidate_lists(SphContext* c) { c->lists_valid = false; c->bricks_valid = false; c->brec_valid = false; c->stg_kind = 0; c->k_kind = 0; }
+// particle positions / order / flags changed: neighbour lists and the non-empty-brick list are stale
+static inline void sph_invalidate_lists(SphContext* c) { sphd_invalidate(c->dv); }
 int sph_fail(SphContext* c, int code, const char* what);
 // the particle SET changed (records appended / dropped / re-selected): whatever a device-side check established about it is void
 static inline void sph_forget_pure_fluid(SphContext* c) { c->pure_fluid = 0; c->pure_fluid_n = -1; }
@@ -237,7 +226,7 @@ int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, dou
 int sphk_rigid_apply16(SphContext* c, int object_id, const double* sums, int mode);
 int sphk_scatter_rest(SphContext* c, const int* pid_dev, const float* x0_dev, int n);
 struct BrickListArgs;
-int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a);  // sph_gather.hip: what the sort's place kernel needs to build the step's brick list
+int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a, SphPartKey* key);  // sph_gather.hip: what the sort's place kernel needs to build the step's brick list, and the key it will serve
 int sphk_gather(SphContext* c, int mode);
 int sphk_gather_layers(SphContext* c, int mode, int lo, int hi, int lo2, int hi2);  // brick sweep, targets in x layers [lo,hi) u [lo2,hi2)
 int sphk_pack_advected(SphContext* c, int first, int count, void* dst);

@@ -225,7 +225,7 @@ int sphk_hash_histogram(SphContext* c) {
     c->cell_cur ^= 1;
     c->cell_end = nxt;
     c->next_cells_zero = false;
-    c->brick_count_zero = c->N > 0;
+    sphd_count_zeroed(c->dv, c->N > 0);
     if (c->N > 0) {
         DevView d = sph_view(c);
         hipLaunchKernelGGL(k_hash_histogram, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, c->cell_end,
@@ -256,9 +256,10 @@ int sphk_sort_scatter(SphContext* c, bool sort_acc) {
     int4* zero_dst = reinterpret_cast<int4*>(c->cell_buf[c->cell_cur ^ 1]);
     const int zero_n4 = c->scan_blocks * SCAN_TILE / 4;
     BrickListArgs bl;
-    int rc = sphk_brick_list_prepare(c, &bl);
+    SphPartKey bl_key;
+    int rc = sphk_brick_list_prepare(c, &bl, &bl_key);
     if (rc) return rc;
-    if (bl.nblocks > 0 && !c->brick_count_zero) {  // (a sort without its own hash pass: sph_counting_sort called twice)
+    if (bl.nblocks > 0 && !sphd_count_is_zero(c->dv)) {  // (a sort without its own hash pass: sph_counting_sort called twice)
         SPH_HIP(c, hipMemsetAsync(c->brick_count, 0, 2 * sizeof(int), c->stream));
     }
     CellIdx16 off_ix;
@@ -284,11 +285,7 @@ int sphk_sort_scatter(SphContext* c, bool sort_acc) {
     SPH_LAUNCH_CHECK(c);
     c->next_cells_zero = true;
     c->cur = o;
-    sph_invalidate_lists(c);
-    c->brick_count_zero = false;
-    c->bricks_valid = bl.nblocks > 0;  // (key recorded by sphk_brick_list_prepare)
-    c->gcnt_written = false;
-    c->aux_stale = false;  // (eos2 is in the old order: whoever needed density / pressure called sph_ensure_aux before)
+    sphd_sorted(c->dv, bl.nblocks > 0, bl_key);
     if (sort_acc) {
         float4* t = c->acc;
         c->acc = c->acc_tmp;

@@ -36,7 +36,7 @@ if has pmc; then
   head -c 1500 $OUT/pmc_brief.json
 fi
 if has pmcdf; then   # HBM traffic of the DFSPH sweeps (FETCH_SIZE / WRITE_SIZE passes over bench.py --solver dfsph) -> profiles/pmc_traffic_dfsph.json
-  PMC_PASSES="fetch write" bash tools/gpu_pmc.sh ${TAG}_dfsph --solver dfsph > $OUT/pmc_dfsph.log 2>&1; tail -n 2 $OUT/pmc_dfsph.log
+  PMC_PASSES="fetch write" bash tools/gpu_pmc.sh ${TAG}_dfsph --solver dfsph --full > $OUT/pmc_dfsph.log 2>&1; tail -n 2 $OUT/pmc_dfsph.log
   python tools/refresh_pmc.py gpurun_out/pmc_${TAG}_dfsph $OUT/pmc_traffic_dfsph.json --solver dfsph --tail 0 > $OUT/pmc_dfsph_brief.json 2> $OUT/refresh_dfsph.err; echo "refresh dfsph rc=$?"
   rm -rf gpurun_out/pmc_${TAG}_dfsph
   cp $OUT/pmc_traffic_dfsph.json profiles/pmc_traffic_dfsph.json
