@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 5
+#define SPH_ABI_VERSION 6
 
 typedef struct SphContext SphContext;
 
@@ -445,6 +445,40 @@ int32_t sph_dfsph_step(SphContext* ctx, int32_t n_steps, const int32_t* dynamic_
  * layers' velocities from their owners. */
 int32_t sph_dfsph_compute_density_error_range(SphContext* ctx, float offset, int32_t first, int32_t count, double* out);
 int32_t sph_copy_velocity_records(SphContext* ctx, int32_t first, int32_t count, void* device_buf, int32_t to_context);
+
+/* ======================================================================================
+ * Headless frame export (run_simulation.py:37-98 of the reference: the window, its camera, scene.particles,
+ * scene.lines, window.write_image): a sphere-impostor point renderer with a depth buffer, on the device, next to
+ * the particles; only the finished 8-bit image crosses PCIe.  Three launches per frame (clear; splat -- plus one
+ * over the compacted list of large sprites; box + resolve), all on the context's stream, so a frame is ordered
+ * behind the steps before it without a synchronisation.  A frame READS the particle state and writes none of it.
+ * The image is a per-pixel 64-bit minimum of (depth bits << 32 | rgb), which does not depend on particle order or
+ * scheduling: frames are bit-reproducible.  csrc/sph_render.hip states the arithmetic operation by operation.
+ * Key, image and depth buffers are allocated by the first frame call (and again when the size changes) and freed
+ * by the context's destructor.  Single-domain contexts only: a slab rank answers SPH_E_STATE.
+ * ==================================================================================== */
+#define SPH_RENDER_MAX_INVISIBLE 32
+typedef struct SphRenderParams {
+    int32_t width, height;          /* 1024 x 1024: the reference's window (run_simulation.py:37) */
+    float eye[3], lookat[3], up[3]; /* (5.5, 2.5, 4.0), (-1, 0, 0), (0, 1, 0)   run_simulation.py:41-43 */
+    float fov_y_deg;                /* 70                                        run_simulation.py:44 */
+    float radius;                   /* world radius of a particle's sphere: particle_radius (run_simulation.py:91) */
+    float near_plane;               /* > 0: particles whose centre is nearer along the view direction draw nothing */
+    float light[3];                 /* point light, white: (2, 2, 2)             run_simulation.py:90 */
+    float ambient;                  /* in [0, 1]: shade = ambient + (1 - ambient) max(0, n.l) */
+    uint8_t background[3], draw_box;/* (0, 0, 0); draw_box != 0: the twelve edges of the box (0,0,0)-box_end */
+    float box_end[3];               /* domainEnd                                 run_simulation.py:59-69 */
+    float box_color[3];             /* (0.99, 0.68, 0.28)                        run_simulation.py:93 */
+} SphRenderParams;
+/* SPH_E_INVALID: width or height outside [1, 16384], eye == lookat, up zero or parallel to the view direction, fov not in
+ * (0, 180), radius / near_plane not positive, ambient outside [0, 1], a non-finite number. */
+int32_t sph_render_set_params(SphContext* ctx, const SphRenderParams* params);
+/* particles of these objects are not drawn (invisibleObjects of the scene file); n <= SPH_RENDER_MAX_INVISIBLE, n = 0 clears */
+int32_t sph_render_set_invisible(SphContext* ctx, const int32_t* object_ids, int32_t n);
+int32_t sph_render_frame(SphContext* ctx);                                  /* enqueues; needs sph_render_set_params before */
+int32_t sph_render_download(SphContext* ctx, uint8_t* rgb, size_t bytes);   /* u8 [height, width, 3], row 0 at the top; synchronises */
+/* f32 [height, width]: distance along the view direction of what the pixel shows, +inf where nothing was drawn; synchronises */
+int32_t sph_render_download_depth(SphContext* ctx, float* depth, size_t bytes);
 
 #ifdef __cplusplus
 }

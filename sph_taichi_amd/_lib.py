@@ -51,6 +51,16 @@ class SphDfsphStats(C.Structure):
                 ("steps", C.c_int64)]
 
 
+class SphRenderParams(C.Structure):
+    """Mirror of `struct SphRenderParams` (include/sph_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("eye", _F3), ("lookat", _F3), ("up", _F3),
+                ("fov_y_deg", C.c_float), ("radius", C.c_float), ("near_plane", C.c_float), ("light", _F3),
+                ("ambient", C.c_float), ("background", C.c_uint8 * 3), ("draw_box", C.c_uint8),
+                ("box_end", _F3), ("box_color", _F3)]
+
+
+RENDER_MAX_INVISIBLE = 32
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -61,7 +71,7 @@ OPT_GATHER_IMPL, OPT_TIMING, OPT_FUSED_STEP, OPT_BRICK_SHAPE, OPT_NO_DYNAMIC_SOL
 VAR_GROUPS, VAR_GAT_LDS, VAR_GAT_LDS4, VAR_FORCE_BF, VAR_DEEP, VAR_MFMA = 1, 2, 4, 8, 16, 32
 VAR_DEFAULT = VAR_GROUPS | VAR_FORCE_BF | VAR_DEEP
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol include/sph_hip.h declares: (name, restype, argtypes)
 _ctx = C.c_void_p
@@ -151,6 +161,11 @@ SYMBOLS = [
     ("sph_comm_sync", C.c_int32, [_ctx, C.c_void_p]),
     ("sph_comm_halo_time", C.c_int32, [_ctx, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     ("sph_comm_info", C.c_int32, [_ctx, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("sph_render_set_params", C.c_int32, [_ctx, C.POINTER(SphRenderParams)]),
+    ("sph_render_set_invisible", C.c_int32, [_ctx, C.POINTER(C.c_int32), C.c_int32]),
+    ("sph_render_frame", C.c_int32, [_ctx]),
+    ("sph_render_download", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_render_download_depth", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
 ]
 
 _LIB = None

@@ -81,6 +81,7 @@ struct DevView {
     float* rigid_rest_cm;
 };
 
+struct SphRender;   // frame export (sph_render.hip): camera, invisible set, key / image / depth buffers; null until sph_render_set_params
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -191,6 +192,7 @@ struct SphContext {
     int ev_used;
     bool slab_ev_open;  // slab mode: events [0..2] of ev[ev_used] are recorded, [3..4] follow in sph_slab_forces
     SphTimings tm;
+    SphRender* render;
     char err[512];
 };
 
@@ -251,6 +253,7 @@ int sphk_rigid_solve(SphContext* c, int object_id);
 int sphk_rigid_solve_all(SphContext* c, const int* ids, int n_ids, bool advect_first);  // every dynamic body + the solid wall passes, batched
 int sphk_extract(SphContext* c, int field, void* dst);
 int sphk_insert(SphContext* c, int field, const void* src);
+void sph_render_release(SphContext* c);  // sph_render.hip: frees the frame-export buffers (sph_destroy)
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -1,0 +1,452 @@
+// sph_render.hip -- headless frame export: what the reference's window shows (run_simulation.py:37-98: scene.particles
+// with per-vertex colour under one point light, scene.lines for the domain box, window.write_image), rendered on the
+// device from the context's own records.  Sphere impostors with a depth buffer; no reference kernel is replaced (the
+// reference hands its vis buffers to Taichi's GGUI rasteriser).
+//
+// Launches per frame (all on the context's stream; particle state is read, never written):
+//   k_render_clear    every pixel key = 0xFFFFFFFF'00000000 | background; the large-sprite counter = 0
+//   k_render_splat    one lane per particle: sprites of pixel radius <= SPH_RENDER_SMALL_R are rasterised by their lane,
+//                     larger ones are appended to a compacted index list (in the context's staging buffer, which is idle
+//                     between an upload / download and the next); the launch's LAST blocks rasterise the box edges,
+//                     one lane per sample
+//   k_render_large    one WAVE per listed particle, lanes striding over the sprite's bounding box (grid-stride over the
+//                     list: the count never visits the host)
+//   k_render_resolve  keys -> u8 [H, W, 3] and f32 depth [H, W]
+// Every loop is bounded: the bounding box is clamped to the image and to SPH_RENDER_MAX_R pixels around the centre (a
+// sprite larger than that is cropped to that square), particles inside the near plane or with a non-finite projection
+// are culled.
+//
+// Order independence: a pixel ends as the MINIMUM over all fragments of key = depth bits << 32 | rgb (positive floats
+// order as their bit patterns); a fragment's key depends on its particle and its pixel only.  Integer min is
+// associative and commutative, so neither particle order nor scheduling can change a bit of the image.  (Two fragments
+// of equal depth: the smaller rgb wins -- still a function of the set.)  The early-out read is safe because keys only
+// ever decrease.
+//
+// ---- THE ARITHMETIC (tests/render_model.py follows this block line by line) ----------------------------------------
+// Everything below is IEEE binary32, one rounding per written operation, evaluated left to right with the parentheses
+// shown; no contraction (pragma below), correctly rounded divide and sqrt (the compiler's default for HIP).
+// dot(a, d) := (a.x * d.x + a.y * d.y) + a.z * d.z.
+//
+// Host, in binary64 (render.py view_basis() is the same sequence), then rounded once to binary32:
+//   f  = lookat - eye;  f = f / sqrt((f.x f.x + f.y f.y) + f.z f.z)                          forward
+//   r  = (f.y up.z - f.z up.y,  f.z up.x - f.x up.z,  f.x up.y - f.y up.x);  r = r / sqrt((r.x r.x + r.y r.y) + r.z r.z)
+//   u  = (r.y f.z - r.z f.y,  r.z f.x - r.x f.z,  r.x f.y - r.y f.x)
+//   focal = (height * 0.5) / tan((fov_y_deg * (3.141592653589793 / 180)) * 0.5)
+// Host, binary32: cx = width * 0.5, cy = height * 0.5, r2 = radius * radius, dl = light - eye,
+//   L = (dot(r, dl), dot(u, dl), dot(f, dl)), fr = focal * radius.
+//
+// Particle (position x, colour c[3] as integers, visible object, index < particle count):
+//   d = x - eye;  a = dot(r, d);  b = dot(u, d);  zc = dot(f, d)
+//   cull unless zc >= near
+//   px = cx + (focal * a) / zc;  py = cy - (focal * b) / zc;  R = fr / zc;  inv = zc / focal
+//   cull unless px, py and R are finite
+//   Rb = min(R, SPH_RENDER_MAX_R)
+//   columns i in [max(ceil((px - Rb) - 0.5), 0), min(floor((px + Rb) - 0.5), width - 1)], rows j likewise with py, height
+//   kc[k] = float(c[k]) / 255
+// Fragment (pixel i, j):
+//   dx = ((i + 0.5) - px) * inv;  dy = (py - (j + 0.5)) * inv                 view units, y up
+//   h2 = (r2 - dx * dx) - dy * dy;  skip unless h2 >= 0;  hh = sqrt(h2)
+//   z = zc - hh;  skip unless z > 0
+//   n = (dx / radius, dy / radius, hh / radius)
+//   l = (L.x - (a + dx), L.y - (b + dy), z - L.z)                            surface point -> light; third axis towards the eye
+//   ll = sqrt((l.x l.x + l.y l.y) + l.z l.z);  nl = ll > 0 ? ((n.x l.x + n.y l.y) + n.z l.z) / ll : 0
+//   s = ambient + (1 - ambient) * max(nl, 0)
+//   q[k] = uint(min(max(kc[k] * s, 0), 1) * 255 + 0.5)                       truncation
+//   key = bits(z) << 32 | q[0] << 16 | q[1] << 8 | q[2];  pixel key = min(pixel key, key)
+// Box edge e = (A, B) of the twelve, sample m of S = 4 (width + height):
+//   t = (m + 0.5) / S;  P = A + (B - A) * t;  d = P - eye;  a, b, zc as above;  skip unless zc >= near
+//   px = cx + (focal * a) / zc;  py = cy - (focal * b) / zc;  skip unless 0 <= px < width and 0 <= py < height
+//   i = int(px), j = int(py);  key = bits(zc) << 32 | box rgb, box rgb[k] = uint(min(max(box_color[k], 0), 1) * 255 + 0.5)
+// Resolve: rgb = low 24 bits of the key; depth = float of the high 32 bits, +inf where they are 0xFFFFFFFF.
+#include <math.h>
+#include <new>
+
+#include "sph_internal.h"
+
+#pragma clang fp contract(off)
+
+#define SPH_RENDER_SMALL_R 4.0f    // sprites up to this pixel radius (at most 9 x 9 pixels) are rasterised by one lane
+#define SPH_RENDER_MAX_R 512.0f    // larger sprites are cropped to the square of this half-width around their centre
+#define SPH_RENDER_MAX_DIM 16384
+#define RTPB 256
+
+struct RenderCam {
+    int W, H, S;              // image size; samples per box edge
+    int n_invisible;
+    int invisible[SPH_RENDER_MAX_INVISIBLE];
+    float ex, ey, ez;
+    float rx, ry, rz, ux, uy, uz, fx, fy, fz;
+    float focal, cx, cy, radius, r2, fr, near_plane;
+    float Lx, Ly, Lz, ambient;
+    float bex, bey, bez;      // box_end
+    unsigned box_rgb, background;
+    int draw_box;
+};
+
+struct SphRender {
+    SphRenderParams p;
+    RenderCam cam;
+    int W, H;                              // what the buffers below are sized for
+    unsigned long long* keys;              // [W * H]
+    unsigned* big_count;                   // device counter of the large-sprite list
+    unsigned char* rgb;                    // [H * W * 3]
+    float* depth;                          // [H * W]
+    bool have_frame;
+};
+
+struct Sprite { float a, b, zc, px, py, inv; int i0, i1, j0, j1; float R; };
+
+__device__ __forceinline__ float rdot(float ax, float ay, float az, float dx, float dy, float dz) { return (ax * dx + ay * dy) + az * dz; }
+
+__device__ __forceinline__ bool render_visible(const RenderCam& cam, int flags) {
+    const int oid = sph_flags_object(flags);
+    for (int k = 0; k < cam.n_invisible; ++k)
+        if (cam.invisible[k] == oid) return false;
+    return true;
+}
+
+// projection and clamped bounding box of one particle; false = culled
+__device__ __forceinline__ bool render_sprite(const RenderCam& cam, float x, float y, float z, Sprite& s) {
+    const float dx = x - cam.ex, dy = y - cam.ey, dz = z - cam.ez;
+    s.a = rdot(cam.rx, cam.ry, cam.rz, dx, dy, dz);
+    s.b = rdot(cam.ux, cam.uy, cam.uz, dx, dy, dz);
+    s.zc = rdot(cam.fx, cam.fy, cam.fz, dx, dy, dz);
+    if (!(s.zc >= cam.near_plane)) return false;
+    s.px = cam.cx + (cam.focal * s.a) / s.zc;
+    s.py = cam.cy - (cam.focal * s.b) / s.zc;
+    s.R = cam.fr / s.zc;
+    s.inv = s.zc / cam.focal;
+    if (!(isfinite(s.px) && isfinite(s.py) && isfinite(s.R))) return false;
+    const float Rb = fminf(s.R, SPH_RENDER_MAX_R);
+    // clamped in float first: the conversions below see values in [-1, 16384] (a sprite beside the image: an empty range)
+    s.i0 = (int)fminf(fmaxf(ceilf((s.px - Rb) - 0.5f), 0.0f), (float)cam.W);
+    s.i1 = (int)fmaxf(fminf(floorf((s.px + Rb) - 0.5f), (float)(cam.W - 1)), -1.0f);
+    s.j0 = (int)fminf(fmaxf(ceilf((s.py - Rb) - 0.5f), 0.0f), (float)cam.H);
+    s.j1 = (int)fmaxf(fminf(floorf((s.py + Rb) - 0.5f), (float)(cam.H - 1)), -1.0f);
+    return s.i0 <= s.i1 && s.j0 <= s.j1;
+}
+
+__device__ __forceinline__ void render_fragment(const RenderCam& cam, unsigned long long* __restrict__ keys, const Sprite& s,
+                                                const float kc[3], int i, int j) {
+    const float dx = (((float)i + 0.5f) - s.px) * s.inv;
+    const float dy = (s.py - ((float)j + 0.5f)) * s.inv;
+    const float h2 = (cam.r2 - dx * dx) - dy * dy;
+    if (!(h2 >= 0.0f)) return;
+    const float hh = sqrtf(h2);
+    const float z = s.zc - hh;
+    if (!(z > 0.0f)) return;
+    const float nx = dx / cam.radius, ny = dy / cam.radius, nz = hh / cam.radius;
+    const float lx = cam.Lx - (s.a + dx), ly = cam.Ly - (s.b + dy), lz = z - cam.Lz;
+    const float ll = sqrtf((lx * lx + ly * ly) + lz * lz);
+    const float nl = ll > 0.0f ? ((nx * lx + ny * ly) + nz * lz) / ll : 0.0f;
+    const float shade = cam.ambient + (1.0f - cam.ambient) * fmaxf(nl, 0.0f);
+    unsigned rgb = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float t = fminf(fmaxf(kc[k] * shade, 0.0f), 1.0f);
+        rgb = (rgb << 8) | (unsigned)(t * 255.0f + 0.5f);
+    }
+    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | rgb;
+    unsigned long long* p = keys + (size_t)j * cam.W + i;      // 0 <= i < W, 0 <= j < H by the clamped box
+    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+}
+
+__device__ __forceinline__ void render_colour(const int* __restrict__ color_cold, int pid, int cold_cap, float kc[3]) {
+    const bool ok = pid >= 0 && pid < cold_cap;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) kc[k] = ok ? (float)color_cold[3 * (size_t)pid + k] / 255.0f : 0.0f;
+}
+
+__global__ __launch_bounds__(RTPB) void k_render_clear(unsigned long long* __restrict__ keys, int n_pix, unsigned background,
+                                                       unsigned* __restrict__ big_count) {
+    const int i = blockIdx.x * RTPB + threadIdx.x;
+    if (i == 0) *big_count = 0u;
+    if (i < n_pix) keys[i] = 0xFFFFFFFF00000000ull | background;
+}
+
+__device__ __forceinline__ void render_box_sample(const RenderCam& cam, unsigned long long* __restrict__ keys, int t) {
+    if (t >= 12 * cam.S) return;
+    const int e = t / cam.S, m = t - e * cam.S;
+    // edge e: axis e / 4, the four edges along it told apart by the two other coordinates (0 or box_end)
+    const int axis = e >> 2, c1 = e & 1, c2 = (e >> 1) & 1;
+    const float end[3] = {cam.bex, cam.bey, cam.bez};
+    float A[3], B[3];
+    const int o1 = (axis + 1) % 3, o2 = (axis + 2) % 3;
+    A[axis] = 0.0f; B[axis] = end[axis];
+    A[o1] = B[o1] = c1 ? end[o1] : 0.0f;
+    A[o2] = B[o2] = c2 ? end[o2] : 0.0f;
+    const float tt = ((float)m + 0.5f) / (float)cam.S;
+    const float dx = (A[0] + (B[0] - A[0]) * tt) - cam.ex, dy = (A[1] + (B[1] - A[1]) * tt) - cam.ey, dz = (A[2] + (B[2] - A[2]) * tt) - cam.ez;
+    const float a = rdot(cam.rx, cam.ry, cam.rz, dx, dy, dz);
+    const float b = rdot(cam.ux, cam.uy, cam.uz, dx, dy, dz);
+    const float zc = rdot(cam.fx, cam.fy, cam.fz, dx, dy, dz);
+    if (!(zc >= cam.near_plane)) return;
+    const float px = cam.cx + (cam.focal * a) / zc;
+    const float py = cam.cy - (cam.focal * b) / zc;
+    if (!(px >= 0.0f && px < (float)cam.W && py >= 0.0f && py < (float)cam.H)) return;   // (false for NaN too)
+    const int i = (int)px, j = (int)py;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(zc) << 32) | cam.box_rgb;
+    unsigned long long* p = keys + (size_t)j * cam.W + i;
+    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+}
+
+// blocks [0, particle_blocks): one lane per particle; blocks behind them: one lane per box-edge sample
+__global__ __launch_bounds__(RTPB) void k_render_splat(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ vf,
+                                                       const float4* __restrict__ aux, const int* __restrict__ color_cold, int N,
+                                                       int cold_cap, int particle_blocks, unsigned long long* __restrict__ keys,
+                                                       int* __restrict__ big_list, unsigned* __restrict__ big_count, int big_cap) {
+    if ((int)blockIdx.x >= particle_blocks) {
+        render_box_sample(cam, keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
+        return;
+    }
+    const int p = blockIdx.x * RTPB + threadIdx.x;
+    if (p >= N) return;
+    if (!render_visible(cam, __float_as_int(vf[p].w))) return;
+    const float4 x = xm[p];
+    Sprite s;
+    if (!render_sprite(cam, x.x, x.y, x.z, s)) return;
+    if (s.R > SPH_RENDER_SMALL_R) {
+        const unsigned slot = atomicAdd(big_count, 1u);
+        if (slot < (unsigned)big_cap) big_list[slot] = p;    // (each particle is listed at most once and big_cap >= N)
+        return;
+    }
+    float kc[3];
+    render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+    for (int j = s.j0; j <= s.j1; ++j)           // at most 9 x 9: R <= SPH_RENDER_SMALL_R
+        for (int i = s.i0; i <= s.i1; ++i) render_fragment(cam, keys, s, kc, i, j);
+}
+
+__global__ __launch_bounds__(RTPB) void k_render_large(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ aux,
+                                                       const int* __restrict__ color_cold, int N, int cold_cap,
+                                                       unsigned long long* __restrict__ keys, const int* __restrict__ big_list,
+                                                       const unsigned* __restrict__ big_count, int big_cap) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * RTPB + threadIdx.x) >> 6, n_waves = (gridDim.x * RTPB) >> 6;
+    unsigned n = *big_count;
+    if (n > (unsigned)big_cap) n = (unsigned)big_cap;
+    for (unsigned w = (unsigned)wave; w < n; w += (unsigned)n_waves) {
+        const int p = big_list[w];
+        if (p < 0 || p >= N) continue;
+        const float4 x = xm[p];
+        Sprite s;
+        if (!render_sprite(cam, x.x, x.y, x.z, s)) continue;
+        float kc[3];
+        render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+        const int bw = s.i1 - s.i0 + 1, bh = s.j1 - s.j0 + 1;   // each <= 2 * SPH_RENDER_MAX_R + 1
+        for (int t = lane; t < bw * bh; t += 64) {
+            const int jj = t / bw;
+            render_fragment(cam, keys, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
+        }
+    }
+}
+
+__global__ __launch_bounds__(RTPB) void k_render_resolve(const unsigned long long* __restrict__ keys, int n_pix,
+                                                         unsigned char* __restrict__ rgb, float* __restrict__ depth) {
+    const int i = blockIdx.x * RTPB + threadIdx.x;
+    if (i >= n_pix) return;
+    const unsigned long long k = keys[i];
+    const unsigned hi = (unsigned)(k >> 32), lo = (unsigned)k;
+    rgb[3 * (size_t)i + 0] = (unsigned char)(lo >> 16);
+    rgb[3 * (size_t)i + 1] = (unsigned char)(lo >> 8);
+    rgb[3 * (size_t)i + 2] = (unsigned char)lo;
+    depth[i] = hi == 0xFFFFFFFFu ? __uint_as_float(0x7F800000u) : __uint_as_float(hi);
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------
+static unsigned pack_unit_rgb(const float c[3]) {
+    unsigned rgb = 0;
+    for (int k = 0; k < 3; ++k) {
+        const float t = fminf(fmaxf(c[k], 0.0f), 1.0f);
+        rgb = (rgb << 8) | (unsigned)(t * 255.0f + 0.5f);
+    }
+    return rgb;
+}
+
+static float hdot(const float a[3], const float d[3]) { return (a[0] * d[0] + a[1] * d[1]) + a[2] * d[2]; }
+
+// the comment block's host part; a message = what is wrong with the parameters
+static const char* make_camera(const SphRenderParams& p, RenderCam& cam) {
+    if (p.width < 1 || p.height < 1 || p.width > SPH_RENDER_MAX_DIM || p.height > SPH_RENDER_MAX_DIM)
+        return "sph_render_set_params: width and height must be in [1, 16384]";
+    const float* all[] = {p.eye, p.lookat, p.up, p.light, p.box_end, p.box_color};
+    for (const float* v : all)
+        for (int k = 0; k < 3; ++k)
+            if (!isfinite(v[k])) return "sph_render_set_params: non-finite vector component";
+    if (!(p.fov_y_deg > 0.0f && p.fov_y_deg < 180.0f)) return "sph_render_set_params: fov_y_deg must be in (0, 180)";
+    if (!(p.radius > 0.0f) || !isfinite(p.radius)) return "sph_render_set_params: radius must be positive";
+    if (!(p.near_plane > 0.0f) || !isfinite(p.near_plane)) return "sph_render_set_params: near_plane must be positive";
+    if (!(p.ambient >= 0.0f && p.ambient <= 1.0f)) return "sph_render_set_params: ambient must be in [0, 1]";
+    double f[3], r[3], u[3], up[3];
+    for (int k = 0; k < 3; ++k) { f[k] = (double)p.lookat[k] - (double)p.eye[k]; up[k] = (double)p.up[k]; }
+    const double fl = sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+    if (!(fl > 0.0)) return "sph_render_set_params: eye == lookat";
+    for (int k = 0; k < 3; ++k) f[k] = f[k] / fl;
+    r[0] = f[1] * up[2] - f[2] * up[1];
+    r[1] = f[2] * up[0] - f[0] * up[2];
+    r[2] = f[0] * up[1] - f[1] * up[0];
+    const double rl = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    const double ul = sqrt((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2]);
+    if (!(ul > 0.0) || !(rl > 1e-6 * ul)) return "sph_render_set_params: up is zero or parallel to the view direction";
+    for (int k = 0; k < 3; ++k) r[k] = r[k] / rl;
+    u[0] = r[1] * f[2] - r[2] * f[1];
+    u[1] = r[2] * f[0] - r[0] * f[2];
+    u[2] = r[0] * f[1] - r[1] * f[0];
+    const double focal = ((double)p.height * 0.5) / tan(((double)p.fov_y_deg * (3.141592653589793 / 180.0)) * 0.5);
+    memset(&cam, 0, sizeof(cam));
+    cam.W = p.width; cam.H = p.height; cam.S = 4 * (p.width + p.height);
+    cam.ex = p.eye[0]; cam.ey = p.eye[1]; cam.ez = p.eye[2];
+    const float rf[3] = {(float)r[0], (float)r[1], (float)r[2]}, uf[3] = {(float)u[0], (float)u[1], (float)u[2]},
+                ff[3] = {(float)f[0], (float)f[1], (float)f[2]};
+    cam.rx = rf[0]; cam.ry = rf[1]; cam.rz = rf[2];
+    cam.ux = uf[0]; cam.uy = uf[1]; cam.uz = uf[2];
+    cam.fx = ff[0]; cam.fy = ff[1]; cam.fz = ff[2];
+    cam.focal = (float)focal;
+    if (!(cam.focal > 0.0f) || !isfinite(cam.focal)) return "sph_render_set_params: fov_y_deg gives no usable focal length";
+    cam.cx = (float)p.width * 0.5f; cam.cy = (float)p.height * 0.5f;
+    cam.radius = p.radius; cam.r2 = p.radius * p.radius; cam.fr = cam.focal * p.radius; cam.near_plane = p.near_plane;
+    const float dl[3] = {p.light[0] - p.eye[0], p.light[1] - p.eye[1], p.light[2] - p.eye[2]};
+    cam.Lx = hdot(rf, dl); cam.Ly = hdot(uf, dl); cam.Lz = hdot(ff, dl);
+    cam.ambient = p.ambient;
+    cam.bex = p.box_end[0]; cam.bey = p.box_end[1]; cam.bez = p.box_end[2];
+    cam.box_rgb = pack_unit_rgb(p.box_color);
+    cam.background = ((unsigned)p.background[0] << 16) | ((unsigned)p.background[1] << 8) | (unsigned)p.background[2];
+    cam.draw_box = p.draw_box ? 1 : 0;
+    return nullptr;
+}
+
+static void render_free_buffers(SphRender* r) {
+    if (r->keys) (void)hipFree(r->keys);
+    if (r->big_count) (void)hipFree(r->big_count);
+    if (r->rgb) (void)hipFree(r->rgb);
+    if (r->depth) (void)hipFree(r->depth);
+    r->keys = nullptr; r->big_count = nullptr; r->rgb = nullptr; r->depth = nullptr;
+    r->W = r->H = 0;
+    r->have_frame = false;
+}
+
+void sph_render_release(SphContext* c) {
+    if (!c->render) return;
+    render_free_buffers(c->render);
+    delete c->render;
+    c->render = nullptr;
+}
+
+// compositing across GPUs is not built: a context that holds a window of the domain refuses
+static bool render_is_slab(const SphContext* c) {
+    return c->p.cell_origin[0] != 0 || c->p.cell_origin[1] != 0 || c->p.cell_origin[2] != 0 || c->p.cold_capacity > 0 ||
+           c->p.grid_num[0] != c->nx_alloc || c->opt_drop_outside || c->in_off != 0;
+}
+
+static SphRender* render_state(SphContext* c) {
+    if (!c->render) {
+        c->render = new (std::nothrow) SphRender();
+        if (c->render) memset(c->render, 0, sizeof(SphRender));
+    }
+    return c->render;
+}
+
+static int render_alloc(SphContext* c, SphRender* r) {
+    const int W = r->cam.W, H = r->cam.H;
+    if (r->keys && r->W == W && r->H == H) return 0;
+    if (r->keys) {   // another size: the old buffers may still be read by an enqueued frame
+        SPH_HIP(c, hipStreamSynchronize(c->stream));
+        render_free_buffers(r);
+    }
+    const size_t n = (size_t)W * H;
+    hipError_t e = hipMalloc((void**)&r->keys, n * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&r->big_count, 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&r->rgb, n * 3);
+    if (e == hipSuccess) e = hipMalloc((void**)&r->depth, n * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        render_free_buffers(r);
+        snprintf(c->err, sizeof(c->err), "sph_render_frame: hipMalloc of the %d x %d frame buffers failed: %s", W, H, hipGetErrorString(e));
+        return SPH_E_NOMEM;
+    }
+    r->W = W; r->H = H;
+    return 0;
+}
+
+extern "C" {
+
+int32_t sph_render_set_params(SphContext* c, const SphRenderParams* params) {
+    if (!c) return SPH_E_INVALID;
+    if (!params) return sph_fail(c, SPH_E_INVALID, "sph_render_set_params: null argument");
+    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_set_params: this context is a slab rank; frames are rendered from single-domain contexts only");
+    RenderCam cam;
+    if (const char* what = make_camera(*params, cam)) return sph_fail(c, SPH_E_INVALID, what);
+    SphRender* r = render_state(c);
+    if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_render_set_params: out of host memory");
+    cam.n_invisible = r->cam.n_invisible;
+    memcpy(cam.invisible, r->cam.invisible, sizeof(cam.invisible));
+    r->p = *params;
+    r->cam = cam;
+    return 0;
+}
+
+int32_t sph_render_set_invisible(SphContext* c, const int32_t* object_ids, int32_t n) {
+    if (!c) return SPH_E_INVALID;
+    if (n < 0 || n > SPH_RENDER_MAX_INVISIBLE || (n > 0 && !object_ids))
+        return sph_fail(c, SPH_E_INVALID, "sph_render_set_invisible: n must be in [0, 32] with a list behind it");
+    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_set_invisible: this context is a slab rank; frames are rendered from single-domain contexts only");
+    SphRender* r = render_state(c);
+    if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_render_set_invisible: out of host memory");
+    r->cam.n_invisible = n;
+    for (int k = 0; k < n; ++k) r->cam.invisible[k] = object_ids[k];
+    return 0;
+}
+
+int32_t sph_render_frame(SphContext* c) {
+    if (!c) return SPH_E_INVALID;
+    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_frame: this context is a slab rank; frames are rendered from single-domain contexts only");
+    SphRender* r = c->render;
+    if (!r || r->cam.W <= 0) return sph_fail(c, SPH_E_STATE, "sph_render_frame needs sph_render_set_params first");
+    SPH_HIP(c, hipSetDevice(c->device));
+    if (int rc = render_alloc(c, r)) return rc;
+    const RenderCam& cam = r->cam;
+    const int n_pix = cam.W * cam.H;     // <= 2^28
+    const int N = c->N;
+    const float4* xm = c->xm[c->cur] + c->in_off;
+    const float4* vf = c->vf[c->cur] + c->in_off;
+    const float4* aux = c->aux[c->cur] + c->in_off;
+    int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity
+    const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
+    hipLaunchKernelGGL(k_render_clear, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, cam.background, r->big_count);
+    SPH_LAUNCH_CHECK(c);
+    const int particle_blocks = (N + RTPB - 1) / RTPB;
+    const int box_blocks = cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
+    if (particle_blocks + box_blocks > 0) {
+        hipLaunchKernelGGL(k_render_splat, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, xm, vf, aux, c->color_cold, N,
+                           c->cold_cap, particle_blocks, r->keys, big_list, r->big_count, big_cap);
+        SPH_LAUNCH_CHECK(c);
+    }
+    if (N > 0) {
+        int blocks = (N + 3) / 4;          // one wave per listed particle, at most 4096 waves striding over the list
+        if (blocks > 1024) blocks = 1024;
+        hipLaunchKernelGGL(k_render_large, dim3(blocks), dim3(RTPB), 0, c->stream, cam, xm, aux, c->color_cold, N, c->cold_cap, r->keys,
+                           big_list, r->big_count, big_cap);
+        SPH_LAUNCH_CHECK(c);
+    }
+    hipLaunchKernelGGL(k_render_resolve, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, r->rgb, r->depth);
+    SPH_LAUNCH_CHECK(c);
+    r->have_frame = true;
+    return 0;
+}
+
+static int render_download(SphContext* c, void* host, size_t bytes, bool depth) {
+    if (!c) return SPH_E_INVALID;
+    SphRender* r = c->render;
+    if (!r || !r->have_frame) return sph_fail(c, SPH_E_STATE, "sph_render_download: no frame has been rendered");
+    const size_t want = (size_t)r->W * r->H * (depth ? 4 : 3);
+    if (!host || bytes != want) return sph_fail(c, SPH_E_INVALID, "sph_render_download: size mismatch (u8 [H, W, 3] / f32 [H, W] of the last frame)");
+    SPH_HIP(c, hipSetDevice(c->device));
+    SPH_HIP(c, hipMemcpyAsync(host, depth ? (const void*)r->depth : (const void*)r->rgb, bytes, hipMemcpyDeviceToHost, c->stream));
+    SPH_HIP(c, hipStreamSynchronize(c->stream));
+    return sph_check_device_flags(c);
+}
+
+int32_t sph_render_download(SphContext* c, uint8_t* rgb, size_t bytes) { return render_download(c, rgb, bytes, false); }
+
+int32_t sph_render_download_depth(SphContext* c, float* depth, size_t bytes) { return render_download(c, depth, bytes, true); }
+
+}  // extern "C"

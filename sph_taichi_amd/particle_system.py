@@ -347,6 +347,35 @@ class ParticleSystem:
             self.rigid_rest_cm.from_numpy(z["rigid_rest_cm"])
         return {k[5:]: z[k] for k in z.files if k.startswith("meta_")}
 
+    # ---- frame export (run_simulation.py:37-98 of the reference: the window; here an image made on the device) ----
+    def render(self, camera=None, invisible_objects=(), size=(1024, 1024)) -> np.ndarray:
+        """The particles as lit spheres of radius `particle_radius` in their objects' colours plus the domain box, seen
+        from `camera` (default: the reference's window camera), as uint8 [H, W, 3] with row 0 at the top; `size` =
+        (width, height).  Rendered on the GPU behind whatever was enqueued before; only the image is copied back.
+        Independent of `GGUI` and of `copy_to_vis_buffer`."""
+        from . import render as _render
+        cam = camera if camera is not None else _render.Camera()
+        rp = _render.render_params(cam, size, self.particle_radius, self.domain_end)
+        self._call("sph_render_set_params", C.byref(rp))
+        ids = [int(i) for i in invisible_objects]
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        self._call("sph_render_set_invisible", arr, len(ids))
+        self._call("sph_render_frame")
+        self._render_shape = (int(size[1]), int(size[0]))
+        out = np.empty(self._render_shape + (3,), dtype=np.uint8)
+        self._call("sph_render_download", out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def render_depth(self) -> np.ndarray:
+        """float32 [H, W] of the last `render`: distance along the view direction of the surface (or box line) each
+        pixel shows, +inf where nothing was drawn."""
+        shape = getattr(self, "_render_shape", None)
+        if shape is None:
+            raise _lib.SphError("render_depth: no frame has been rendered")
+        out = np.empty(shape, dtype=np.float32)
+        self._call("sph_render_download_depth", out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
     def copy_to_vis_buffer(self, invisible_objects=[]):
         """particle_system.py:392-407 (host copy; there is no GGUI here)."""
         assert self.GGUI

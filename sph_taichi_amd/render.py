@@ -1,0 +1,92 @@
+"""Headless frame export: the camera of the reference's window (run_simulation.py:37-45, 90-93), the view basis the
+device renderer uses (csrc/sph_render.hip states the arithmetic), and a PNG writer on zlib + struct.
+
+The picture itself is made on the GPU (`ParticleSystem.render`); nothing here touches particle data.
+"""
+from __future__ import annotations
+
+import math
+import struct
+import zlib
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+
+
+@dataclass
+class Camera:
+    """Defaults = the reference's window: position (5.5, 2.5, 4.0), lookat (-1, 0, 0), up (0, 1, 0), fov 70 degrees,
+    point light (2, 2, 2), black background, box lines (0.99, 0.68, 0.28)  (run_simulation.py:37-50, 90-93)."""
+    eye: tuple = (5.5, 2.5, 4.0)
+    lookat: tuple = (-1.0, 0.0, 0.0)
+    up: tuple = (0.0, 1.0, 0.0)
+    fov_y_deg: float = 70.0
+    near_plane: float = 0.05
+    light: tuple = (2.0, 2.0, 2.0)
+    ambient: float = 0.3
+    background: tuple = (0, 0, 0)
+    draw_box: bool = True
+    box_color: tuple = (0.99, 0.68, 0.28)
+
+
+def view_basis(camera: Camera, height: int):
+    """(right, up, forward, focal) as float32: the binary64 sequence of the comment block of csrc/sph_render.hip, rounded
+    once.  The library runs the same sequence on the same inputs; the tests' model takes these values.  Raises
+    ValueError where the library answers SPH_E_INVALID."""
+    f32 = lambda v: [float(np.float32(c)) for c in v]      # the struct carries binary32
+    eye, lookat, up = f32(camera.eye), f32(camera.lookat), f32(camera.up)
+    f = [lookat[k] - eye[k] for k in range(3)]
+    fl = math.sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2])
+    if not fl > 0.0:
+        raise ValueError("camera: eye == lookat")
+    f = [c / fl for c in f]
+    r = [f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]]
+    rl = math.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
+    ul = math.sqrt((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2])
+    if not ul > 0.0 or not rl > 1e-6 * ul:
+        raise ValueError("camera: up is zero or parallel to the view direction")
+    r = [c / rl for c in r]
+    u = [r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]]
+    fov = float(np.float32(camera.fov_y_deg))
+    if not 0.0 < fov < 180.0:
+        raise ValueError("camera: fov_y_deg must be in (0, 180)")
+    focal = (float(height) * 0.5) / math.tan((fov * (3.141592653589793 / 180.0)) * 0.5)
+    return (np.array(r, dtype=np.float32), np.array(u, dtype=np.float32), np.array(f, dtype=np.float32),
+            np.float32(focal))
+
+
+def render_params(camera: Camera, size, radius: float, box_end) -> "_lib.SphRenderParams":
+    """The C struct for `camera` at `size` = (width, height)."""
+    p = _lib.SphRenderParams()
+    p.width, p.height = int(size[0]), int(size[1])
+    for name in ("eye", "lookat", "up", "light", "box_color"):
+        setattr(p, name, (_lib.C.c_float * 3)(*[float(v) for v in getattr(camera, name)]))
+    p.box_end = (_lib.C.c_float * 3)(*[float(v) for v in box_end])
+    p.fov_y_deg = float(camera.fov_y_deg)
+    p.radius = float(radius)
+    p.near_plane = float(camera.near_plane)
+    p.ambient = float(camera.ambient)
+    p.background = (_lib.C.c_uint8 * 3)(*[int(v) for v in camera.background])
+    p.draw_box = 1 if camera.draw_box else 0
+    return p
+
+
+def _chunk(tag: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def write_png(path: str, rgb: np.ndarray, level: int = 6):
+    """8-bit RGB PNG of a uint8 [H, W, 3] array (row 0 at the top): IHDR, one IDAT (filter 0 on every row), IEND."""
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png: expected uint8 [H, W, 3]")
+    h, w = a.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)         # a filter-type byte in front of every row
+    rows[:, 1:] = a.reshape(h, 3 * w)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n")
+        fh.write(_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        fh.write(_chunk(b"IDAT", zlib.compress(rows.tobytes(), level)))
+        fh.write(_chunk(b"IEND", b""))

@@ -1,12 +1,15 @@
 """Headless counterpart of the reference's run_simulation.py (argument parsing,
-substep loop and exporters of /root/reference/run_simulation.py:12-35, 79-113;
-the GGUI window/camera/render code of :37-74, 82-94, 118 has no counterpart).
+substep loop and exporters of /root/reference/run_simulation.py:12-35, 79-113).
+There is no window (:37, 87, 118); what it would show -- camera, light, particles,
+domain box of :39-74, 90-94 -- is rendered on the GPU into the frames that
+`exportFrame` writes (:27-28, 96-98).
 
     python -m sph_taichi_amd.run_simulation --scene_file data/scenes/dragon_bath.json --frames 100
 
 Per frame: `numberOfStepsPerRenderUpdate` solver steps; every int(0.016/dt)
-frames optional ASCII-PLY particle export (`exportPly`) and OBJ rigid-body export
-(`exportObj`), written where the reference writes them.  `--timing` prints the
+frames optional ASCII-PLY particle export (`exportPly`), OBJ rigid-body export
+(`exportObj`) and PNG frame export (`exportFrame`, without the objects listed in
+`invisibleObjects`), written where the reference writes them.  `--timing` prints the
 per-phase HIP-event breakdown (sort / neighbour / force / integrate).
 """
 from __future__ import annotations
@@ -31,7 +34,7 @@ def write_ply_ascii(path: str, pos: np.ndarray):
         np.savetxt(fh, pos, fmt="%.6f")
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="SPH (MI355X)")
     ap.add_argument("--scene_file", default="", help="scene file")
     ap.add_argument("--frames", type=int, default=100, help="number of frames (the reference loops until the window closes)")
@@ -40,18 +43,36 @@ def main(argv=None):
     ap.add_argument("--dump_npz", default="", help="write the final per-particle state here")
     ap.add_argument("--save_state", default="", help="write a restartable checkpoint (.npz) after the last frame")
     ap.add_argument("--load_state", default="", help="continue from a checkpoint written by --save_state")
-    args = ap.parse_args(argv)
+    ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
+                    help="size of the exportFrame images (the reference's window is 1024 x 1024)")
+    ap.add_argument("--camera", type=float, nargs=6, default=None, metavar=("EX", "EY", "EZ", "LX", "LY", "LZ"),
+                    help="camera position and look-at point of the exportFrame images (default: the reference's window camera)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
     scene_name = scene_path.split("/")[-1].split(".")[0]
     substeps = config.get_cfg("numberOfStepsPerRenderUpdate")
     output_interval = int(0.016 / config.get_cfg("timeStepSize"))
+    output_frames = config.get_cfg("exportFrame")
     output_ply = config.get_cfg("exportPly")
     output_obj = config.get_cfg("exportObj")
     series_prefix = "{}_output/particle_object_{}.ply".format(scene_name, "{}")
+    if output_frames:
+        os.makedirs(f"{scene_name}_output_img", exist_ok=True)
     if output_ply or output_obj:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
+    invisible_objects = config.get_cfg("invisibleObjects") or []
+    camera = None
+    if output_frames:
+        from .render import Camera, write_png
+        camera = Camera()
+        if args.camera is not None:
+            camera.eye, camera.lookat = tuple(args.camera[:3]), tuple(args.camera[3:])
 
     scene_dir = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(scene_path)))) or "."
     ps = ParticleSystem(config, GGUI=False, device=args.device, scene_dir=scene_dir, verbose=True)
@@ -63,10 +84,18 @@ def main(argv=None):
     if args.timing:
         ps.set_option(_lib.OPT_TIMING, 1)
 
-    cnt = cnt_ply = 0
+    cnt = cnt_ply = frames_written = 0
+    render_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
         solver.step(substeps)
+        if output_frames and cnt % output_interval == 0:
+            ps.sync()                          # the frame's cost, not the steps still in flight before it
+            tr = time.perf_counter()
+            img = ps.render(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size))
+            render_s += time.perf_counter() - tr
+            write_png(f"{scene_name}_output_img/{cnt:06}.png", img)
+            frames_written += 1
         if cnt % output_interval == 0:
             if output_ply:
                 obj_id = 0
@@ -83,6 +112,9 @@ def main(argv=None):
     steps = args.frames * substeps
     report = {"scene": scene_name, "particles": ps.particle_max_num, "steps": steps,
               "steps_per_s": round(steps / dt, 2), "ms_per_step": round(dt / steps * 1e3, 4)}
+    if frames_written:
+        report["frames_written"] = frames_written
+        report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
     if args.timing:
         tm = _lib.SphTimings()
         ps._call("sph_get_timings", tm)
