@@ -34,10 +34,24 @@ persistent id that SPH_OPT_SORT_BY_PID makes both sides use), a plain array copy
 all-reduce), so every rank takes the same number of iterations as the single-domain solver.  Fluid and static
 solids only.
 
-Transports: `TorchTransport` (torch.distributed P2P; backend "nccl" = RCCL on
-ROCm, "gloo" for the CPU tests) and `LocalTransport` (several logical ranks in one
-process on one GPU -- how the slab logic is verified against the single-domain run
-where only one GPU is available).
+One protocol, two servers.  Everything a rank does -- initialise, a WCSPH or DFSPH step, the guard and the re-cut
+that end a step -- is written once, as a generator on `SlabSolver` that posts communication requests:
+("records", packed), ("halo_v", None), ("sum", float), ("sum_tensor", device tensor; in place).  `SlabSolver._serve`
+answers them with the rank's transport (one process per GPU); `run_local_slabs` answers them for several logical
+ranks in one process on one GPU, in lock-step -- how the slab logic is verified against the single-domain run where
+only one GPU is available.
+
+Transports.  A transport is an object with
+    start_counts(n_left, n_right)   post the record counts of the NEXT exchange (non-blocking)
+    resolve_counts()                wait for the neighbours' counts, if any are posted and unread
+    exchange(send_left, n_left, send_right, n_right, alloc) -> (recv_left, n, recv_right, n)
+    swap(send_left, send_right, recv_left, recv_right)      fixed-size exchange with the x-neighbours
+    all_reduce_sum(t)               in-place sum over ranks of a small tensor; returns t when it is complete
+and the class attribute `stream_ordered`: True if exchange() is enqueued behind the packers' event on the device
+(it then takes `after_packers`), False if the host has to wait for the packers first.  `TorchTransport`
+(torch.distributed P2P; backend "nccl" = RCCL on ROCm, "gloo" for the CPU tests) and `NativeTransport` (RCCL behind
+the C ABI) are the two; `SlabSolver.transport is None` means logical ranks: nothing to announce, packers waited for
+on the host.
 
 Dynamic solids.  Scenes with dynamic RigidBlocks / RigidBodies use HALO = 3: the
 moving boundary volumes (sph_base.py:106-113) of ghost layers 1..2 are then
@@ -70,22 +84,10 @@ HALO_DYNAMIC = 3
 RECORD_BYTES = 48
 
 
-class LocalTransport:
-    """Mailbox for P logical ranks driven in lock-step by one process."""
-
-    def __init__(self, world):
-        self.world = world
-        self.box = {}
-
-    def post(self, src, dst, buf, count):
-        self.box[(src, dst)] = (buf, count)
-
-    def take(self, src, dst):
-        return self.box.pop((src, dst), (None, 0))
-
-
 class TorchTransport:
     """torch.distributed point-to-point exchange with the x-neighbours."""
+
+    stream_ordered = False
 
     def __init__(self, device, loopback=False):
         """`loopback` (tests): this rank is its own LEFT neighbour, so every message of the protocol -- the count
@@ -98,6 +100,8 @@ class TorchTransport:
         self.device = device
         self.cpu_staging = dist.get_backend() == "gloo"
         self.loopback = bool(loopback)
+        self._pending = None        # counts posted by start_counts: (works, sent tensors, receive views, buffer, announced)
+        self._resolved = None       # ... once read: ({neighbour: incoming count}, announced)
 
     def _neighbours(self):
         if self.loopback:
@@ -116,26 +120,25 @@ class TorchTransport:
                right: torch.tensor([n_right], dtype=torch.int64, device=dev)}
         both = torch.zeros(2, dtype=torch.int64, device=dev)     # one buffer: both counts come back in ONE device-to-host copy
         cin = {p: both[i:i + 1] for i, p in enumerate((left, right)) if p is not None}
-        self._cin_both = both
         ops = []
         for p in (left, right):
             if p is not None:
                 ops.append(dist.P2POp(dist.isend, out[p], p))
                 ops.append(dist.P2POp(dist.irecv, cin[p], p))
         works = dist.batch_isend_irecv(ops) if ops else []
-        self._pending = (works, out, cin, (n_left, n_right))
+        self._pending = (works, out, cin, both, (n_left, n_right))
 
     def resolve_counts(self):
         """Wait for the counts posted by start_counts and read them (a device-to-host copy each on RCCL).  Called
         while the host would otherwise sit waiting for the packers, so that it is off the exchange's critical path."""
-        if getattr(self, "_pending", None) is None:
+        if self._pending is None:
             return
-        works, _out, cnt_in, announced = self._pending
+        works, _out, cnt_in, both, announced = self._pending
         self._pending = None
         for w in works:
             w.wait()
         left, right = self._neighbours()
-        vals = self._cin_both.tolist() if cnt_in else [0, 0]
+        vals = both.tolist() if cnt_in else [0, 0]
         self._resolved = ({p: int(vals[i]) for i, p in enumerate((left, right)) if p in cnt_in}, announced)
 
     def exchange(self, send_left, n_left, send_right, n_right, alloc):
@@ -145,8 +148,8 @@ class TorchTransport:
         left, right = self._neighbours()
         # 1) counts: posted ahead by start_counts (and usually read already, see resolve_counts), or exchanged
         #    now (first call)
-        if getattr(self, "_resolved", None) is None:
-            if getattr(self, "_pending", None) is None:
+        if self._resolved is None:
+            if self._pending is None:
                 self.start_counts(n_left, n_right)
             self.resolve_counts()
         n_in, announced = self._resolved
@@ -523,7 +526,8 @@ class SlabSolver:
         self.owned_range = None     # (first, count) of the owned particles in the current order
         self.off = None
         self._need_density = True
-        self.transport = None
+        self.transport = None       # None: a logical rank served by run_local_slabs
+        self._packers_pending = False
         self.has_left, self.has_right = rank > 0, rank < world - 1
         self.stats = {"sent": 0, "received": 0}
         self.host_ms = {"forces_pack": 0.0, "exchange": 0.0, "advance": 0.0, "steps": 0}
@@ -620,9 +624,10 @@ class SlabSolver:
         ps._call("sph_slab_forces", bl[0], bl[1], br[0], br[1],
                  fL, nL, C.c_void_p(self.send_buf["L"].data_ptr()),
                  fR, nR, C.c_void_p(self.send_buf["R"].data_ptr()))
-        if getattr(self, "transport", None) is not None and hasattr(self.transport, "resolve_counts"):
-            self.transport.resolve_counts()        # the neighbours' counts, read while the packers are still queued
-        self._packers_pending = pack and bool(getattr(getattr(self, "transport", None), "stream_ordered", False))
+        tr = self.transport
+        if tr is not None:
+            tr.resolve_counts()                    # the neighbours' counts, read while the packers are still queued
+        self._packers_pending = pack and tr is not None and tr.stream_ordered
         if not self._packers_pending:
             ps._call("sph_slab_wait_pack")
         self.stats["sent"] += nL + nR
@@ -661,9 +666,10 @@ class SlabSolver:
         if mode == 1:
             self.ps._call("sph_enforce_boundary_3D", _scene.MATERIAL_SOLID)
 
-    def solve_rigid_bodies(self, mode=1):
+    def _rigid_requests(self, mode):
+        """solve_rigid_body (sph_base.py:247-260) across ranks: per body, one all-reduce of its 16 sums."""
         for oid in self.dynamic_bodies:
-            self.transport.all_reduce_sum(self.rigid_partial(oid, rest=(mode == 0)))
+            yield ("sum_tensor", self.rigid_partial(oid, rest=(mode == 0)))
             self.rigid_apply(oid, mode)
 
     def phase_advance(self, recv_left, n_left, recv_right, n_right, density=True):
@@ -693,10 +699,11 @@ class SlabSolver:
         if not (self._recut_due or self._guard_due):
             self.announce()
 
-    def check_conservation(self):
-        """Collective: sum of the ranks' owned counts == particles of the scene, else RuntimeError on every rank."""
+    def _conservation_requests(self):
+        """Collective (requests): sum of the ranks' owned counts == particles of the scene, else RuntimeError on every rank."""
         t = self.torch.tensor([int(self.owned_range[1])], dtype=self.torch.int64, device=self.tdev)
-        total = int(self.transport.all_reduce_sum(t).item())
+        yield ("sum_tensor", t)
+        total = int(t.item())
         if total != self.n_global:
             raise RuntimeError(f"slab decomposition lost particle conservation at step {self.steps_done}: the ranks own "
                                f"{total} particles, the scene has {self.n_global} (rank {self.rank} owns {self.owned_range[1]}). "
@@ -708,18 +715,18 @@ class SlabSolver:
         self._recut_due = self.recut_every > 0 and (self.steps_done + 1) % self.recut_every == 0
         self._guard_due = self.check_every > 0 and ((self.steps_done + 1) % self.check_every == 0 or self._recut_due)
 
-    def _end_step(self):
+    def _end_step_requests(self):
         """The deferred collectives, then the announcement of the next exchange's counts."""
         if self._guard_due:
-            self.check_conservation()
+            yield from self._conservation_requests()
         if self._recut_due:
-            self.recut_now()                  # (announces)
+            yield from self._recut_requests()  # (announces)
         elif self._guard_due:
             self.announce()
         self._guard_due = False
 
     def announce(self):
-        if getattr(self, "transport", None) is not None and hasattr(self.transport, "start_counts"):
+        if self.transport is not None:
             self.transport.start_counts(*self.next_counts())   # the next exchange's sizes are known now
 
     # -- re-cut (SURVEY 8e: "re-cut every K steps") ------------------------------------------------------
@@ -741,10 +748,10 @@ class SlabSolver:
         self._shift = (new[self.rank] - self.cuts[self.rank], new[self.rank + 1] - self.cuts[self.rank + 1])
         self.cuts = list(new)
 
-    def recut_now(self):
-        """Collective: histogram all-reduce, plan, then announce the next exchange's (possibly deeper) counts."""
+    def _recut_requests(self):
+        """Collective (requests): histogram all-reduce, plan, then announce the next exchange's (possibly deeper) counts."""
         t = self.torch.from_numpy(self.local_histogram()).to(self.tdev)
-        self.transport.all_reduce_sum(t)
+        yield ("sum_tensor", t)
         self.plan_recut(t.cpu().numpy())
         self._recut_due = False
         self.announce()
@@ -770,15 +777,15 @@ class SlabSolver:
         self.ghost = {"L": (0, o[0]), "R": (o[3], o[4] - o[3])}
         self.band = {"L": (o[0], max(o[5] - o[0], 0)), "R": (min(o[6], o[3]), max(o[3] - o[6], 0))}
 
-    # -- torch.distributed driver --------------------------------------------
+    # -- one rank per process: the transport answers ------------------------------
     def attach(self, transport):
         self.transport = transport
 
     def _exchange(self, sL, nL, sR, nR):
         tr = self.transport
-        if getattr(tr, "stream_ordered", False):
+        if tr.stream_ordered:
             # the exchange is enqueued behind the packers' event on the device: nobody waited for them on the host
-            pending, self._packers_pending = getattr(self, "_packers_pending", False), False
+            pending, self._packers_pending = self._packers_pending, False
             return tr.exchange(sL if self.has_left else None, nL, sR if self.has_right else None, nR, self._alloc_recv,
                                after_packers=pending)
         return tr.exchange(sL if self.has_left else None, nL, sR if self.has_right else None, nR, self._alloc_recv)
@@ -850,84 +857,90 @@ class SlabSolver:
             it_p += 1
         self.dfsph_iterations = (it_v, it_p)
         call("sph_dfsph_advect")
-        for oid in self.dynamic_bodies:                       # solve_rigid_body (sph_base.py:247-260) across ranks
-            yield ("sum_tensor", self.rigid_partial(oid))
-            self.rigid_apply(oid, 1)
+        yield from self._rigid_requests(1)
         call("sph_enforce_boundary_3D", _scene.MATERIAL_FLUID)
         recv = yield ("records", self.pack_now())
         self.phase_advance(*recv, density=False)
 
+    def _wcsph_step_requests(self):
+        """One WCSPH step.  `self.host_ms` accumulates where the HOST spends it: enqueueing + waiting for the packers
+        ("forces_pack"), with the record request outstanding ("exchange"), and enqueueing the sort + waiting for its
+        layer offsets, the end of the step included ("advance").  The GPU keeps working through all three (interior
+        force sweep / density sweep), so these are not additive GPU costs; they show whether the exchange stays inside
+        its hiding window.  Meaningful only when a transport serves the rank: under serve_lockstep a request stays
+        outstanding while the other ranks run."""
+        hm = self.host_ms
+        t0 = time.perf_counter()
+        if self.dynamic_bodies:       # the exchange follows the solve: nothing packed by the force phase
+            self.phase_forces(pack=False)
+            yield from self._rigid_requests(1)
+            sent = self.pack_now()
+        else:
+            sent = self.phase_forces()
+        t1 = time.perf_counter()
+        recv = yield ("records", sent)
+        t2 = time.perf_counter()
+        self.phase_advance(*recv)
+        self.steps_done += 1
+        yield from self._end_step_requests()
+        t3 = time.perf_counter()
+        hm["forces_pack"] += (t1 - t0) * 1e3; hm["exchange"] += (t2 - t1) * 1e3; hm["advance"] += (t3 - t2) * 1e3
+        hm["steps"] += 1
+
+    def _step_requests(self):
+        """One step of the scene's solver and the collectives that end it."""
+        self._begin_step()
+        if self.dfsph:
+            yield from self._dfsph_step_requests()
+            self.steps_done += 1
+            yield from self._end_step_requests()
+        else:
+            yield from self._wcsph_step_requests()
+
+    def _initialize_requests(self):
+        """SPHBase.initialize() (sph_base.py:80-85) for a slab: neighbour structure with halos, then the
+        static boundary volumes (ghost layer 1 sees complete neighbourhoods, so owned values are exact)."""
+        self.solver._push()
+        recv = yield ("records", self.init_pack())
+        self.phase_advance(*recv, density=False)
+        yield from self._rigid_requests(0)
+        self.ps._call("sph_compute_boundary_volume", 0)
+        # once more, so that the ghosts carry their owners' boundary volumes into the first step
+        recv = yield ("records", self.init_pack())
+        self.phase_advance(*recv, density=False)
+
     def _serve(self, gen):
         """Drive a request generator with this rank's transport."""
-        tr = self.transport
+        tr, torch = self.transport, self.torch
+        answer = None
         try:
-            req = next(gen)
             while True:
-                kind, arg = req
+                kind, arg = gen.send(answer)
+                answer = None
                 if kind == "halo_v":
                     sL, _ = self.velocity_band("L") if self.has_left else (None, 0)
                     sR, _ = self.velocity_band("R") if self.has_right else (None, 0)
-                    rL = self.torch.empty(self.ghost["L"][1] * 16, dtype=self.torch.uint8, device=self.tdev) if self.has_left else None
-                    rR = self.torch.empty(self.ghost["R"][1] * 16, dtype=self.torch.uint8, device=self.tdev) if self.has_right else None
+                    rL = torch.empty(self.ghost["L"][1] * 16, dtype=torch.uint8, device=self.tdev) if self.has_left else None
+                    rR = torch.empty(self.ghost["R"][1] * 16, dtype=torch.uint8, device=self.tdev) if self.has_right else None
                     tr.swap(sL, sR, rL, rR)
                     self.set_ghost_velocities("L", rL)
                     self.set_ghost_velocities("R", rR)
-                    req = gen.send(None)
                 elif kind == "sum":
-                    t = self.torch.tensor([arg], dtype=self.torch.float64, device=self.tdev)
-                    req = gen.send(float(tr.all_reduce_sum(t).item()))
-                elif kind == "sum_tensor":                    # in place: the body's 16 shape-matching sums
+                    t = torch.tensor([arg], dtype=torch.float64, device=self.tdev)
+                    answer = float(tr.all_reduce_sum(t).item())
+                elif kind == "sum_tensor":                    # in place: a body's 16 sums, the guard's count, the histogram
                     tr.all_reduce_sum(arg)
-                    req = gen.send(None)
                 else:
-                    req = gen.send(self._exchange(*arg))
+                    answer = self._exchange(*arg)
         except StopIteration:
             pass
 
     def step(self, n=1):
-        """`self.host_ms` accumulates where the HOST spends a step: enqueueing + waiting for the packers
-        ("forces_pack"), inside the exchange ("exchange"), and enqueueing the sort + waiting for its layer offsets
-        ("advance").  The GPU keeps working through all three (interior force sweep / density sweep), so these are
-        not additive GPU costs; they show whether the exchange stays inside its hiding window."""
-        import time
-        hm = self.host_ms
-        if self.dfsph:
-            for _ in range(n):
-                self._begin_step()
-                self._serve(self._dfsph_step_requests())
-                self.steps_done += 1
-                self._end_step()
-            return
         for _ in range(n):
-            self._begin_step()
-            t0 = time.perf_counter()
-            if self.dynamic_bodies:
-                self.phase_forces(pack=False)
-                self.solve_rigid_bodies()
-                sent = self.pack_now()
-            else:
-                sent = self.phase_forces()
-            t1 = time.perf_counter()
-            rL, mL, rR, mR = self._exchange(*sent)
-            t2 = time.perf_counter()
-            self.phase_advance(rL, mL, rR, mR)
-            self.steps_done += 1
-            self._end_step()
-            t3 = time.perf_counter()
-            hm["forces_pack"] += (t1 - t0) * 1e3; hm["exchange"] += (t2 - t1) * 1e3; hm["advance"] += (t3 - t2) * 1e3
-            hm["steps"] += 1
+            self._serve(self._step_requests())
 
     def initialize(self):
-        """SPHBase.initialize() (sph_base.py:80-85) for a slab: neighbour structure with halos, then the
-        static boundary volumes (ghost layer 1 sees complete neighbourhoods, so owned values are exact)."""
-        self.solver._push()
-        rL, mL, rR, mR = self._exchange(*self.init_pack())
-        self.phase_advance(rL, mL, rR, mR, density=False)
-        self.solve_rigid_bodies(mode=0)
-        self.ps._call("sph_compute_boundary_volume", 0)
-        # once more, so that the ghosts carry their owners' boundary volumes into the first step
-        rL, mL, rR, mR = self._exchange(*self.init_pack())
-        self.phase_advance(rL, mL, rR, mR, density=False)
+        self._serve(self._initialize_requests())
 
     # -- inspection (tests) ----------------------------------------------------
     def owned(self, names=("pid", "x", "v")):
@@ -939,97 +952,62 @@ class SlabSolver:
 
 
 def run_local_slabs(solvers, n_steps, initialize=False):
-    """Drive P SlabSolvers that live in ONE process (one GPU) in lock-step; a neighbour's send buffer is read
-    directly (device pointer) and the bodies' sums are added on the spot -- what the transports do between ranks."""
-    P = len(solvers)
-
-    def swap(sent):
-        for r, s in enumerate(solvers):
-            s.ps.sync()
-        out = []
-        for r in range(P):
-            rl = (sent[r - 1][2], sent[r - 1][3]) if r > 0 else (None, 0)          # left neighbour's right range
-            rr = (sent[r + 1][0], sent[r + 1][1]) if r + 1 < P else (None, 0)
-            out.append((rl[0], rl[1], rr[0], rr[1]))
-        return out
-
-    def solve_bodies(mode):
-        for oid in solvers[0].dynamic_bodies:
-            total = sum(s.rigid_partial(oid, rest=(mode == 0)).clone() for s in solvers)
-            for s in solvers:
-                s.sums.copy_(total)
-                s.torch.cuda.current_stream().synchronize()
-                s.rigid_apply(oid, mode)
-
-    def exchange_and_advance(sent, density):
-        for s, r in zip(solvers, swap(sent)):
-            s.phase_advance(*r, density=density)
-
-    def recut_if_due():
-        s0 = solvers[0]
-        for s in solvers:
-            s.steps_done += 1
-        owned = sum(int(s.owned_range[1]) for s in solvers)      # the conservation guard of SlabSolver.step
-        if owned != s0.n_global:
-            raise RuntimeError(f"slab decomposition lost particle conservation at step {s0.steps_done}: the slabs own "
-                               f"{owned} particles, the scene has {s0.n_global}")
-        if s0.recut_every > 0 and s0.steps_done % s0.recut_every == 0:
-            hist = sum(s.local_histogram() for s in solvers)
-            for s in solvers:
-                s.plan_recut(hist)
-
+    """Drive P SlabSolvers that live in ONE process (one GPU): `initialize`, or `n_steps` steps."""
     if initialize:
-        for s in solvers:
-            s.solver._push()
-        exchange_and_advance([s.init_pack() for s in solvers], False)
-        solve_bodies(0)
-        for s in solvers:
-            s.ps._call("sph_compute_boundary_volume", 0)
-        exchange_and_advance([s.init_pack() for s in solvers], False)
-        return
-    if solvers[0].dfsph:
-        for _ in range(n_steps):
-            gens = [s._dfsph_step_requests() for s in solvers]
-            reqs = [next(g) for g in gens]
-            while reqs is not None:
-                kind = reqs[0][0]
-                assert all(r[0] == kind for r in reqs), "ranks diverged"
-                if kind == "halo_v":
-                    bands = [{side: (s.velocity_band(side)[0] if ok else None)
-                              for side, ok in (("L", s.has_left), ("R", s.has_right))} for s in solvers]
-                    for r, s in enumerate(solvers):
-                        s.set_ghost_velocities("L", bands[r - 1]["R"] if r > 0 else None)
-                        s.set_ghost_velocities("R", bands[r + 1]["L"] if r + 1 < P else None)
-                    answers = [None] * P
-                elif kind == "sum":
-                    answers = [sum(r[1] for r in reqs)] * P
-                elif kind == "sum_tensor":
-                    total = sum(r[1].clone() for r in reqs)
-                    for s in solvers:
-                        s.sums.copy_(total)
-                        s.torch.cuda.current_stream().synchronize()
-                    answers = [None] * P
-                else:
-                    answers = swap([r[1] for r in reqs])
-                nxt = []
-                for g, a in zip(gens, answers):
-                    try:
-                        nxt.append(g.send(a))
-                    except StopIteration:
-                        nxt.append(None)
-                reqs = None if all(x is None for x in nxt) else nxt
-            recut_if_due()
+        serve_lockstep(solvers, [s._initialize_requests() for s in solvers])
         return
     for _ in range(n_steps):
-        if solvers[0].dynamic_bodies:
-            for s in solvers:
-                s.phase_forces(pack=False)
-            solve_bodies(1)
-            sent = [s.pack_now() for s in solvers]
+        serve_lockstep(solvers, [s._step_requests() for s in solvers])
+
+
+def serve_lockstep(ranks, gens):
+    """Answer the request generators of P logical ranks in lock-step -- what the transports do between processes.  No
+    rank is resumed past a request before all ranks have posted it.  Records: every context is synchronised, then each
+    neighbour gets a COPY of the sender's range -- a rank that is resumed may pack into its send buffer again (initialise
+    does, right away) before the next rank has consumed the answer.  Sums are added in rank order."""
+    import torch
+    P = len(ranks)
+    answers = [None] * P
+    while True:
+        reqs = []
+        for g, a in zip(gens, answers):                       # resume in rank order, up to the next request
+            try:
+                reqs.append(g.send(a))
+            except StopIteration:
+                reqs.append(None)
+        kinds = {None if q is None else q[0] for q in reqs}
+        if len(kinds) != 1:
+            raise RuntimeError(f"ranks diverged: they posted {[None if q is None else q[0] for q in reqs]}")
+        kind, args = kinds.pop(), [None if q is None else q[1] for q in reqs]
+        answers = [None] * P
+        if kind is None:
+            return
+        if kind == "records":
+            for s in ranks:
+                s.ps.sync()
+            copy = lambda buf, n: (buf[: n * RECORD_BYTES].clone(), n)
+            for r in range(P):                                # args[r] = (send_left, n, send_right, n) of rank r
+                rl = copy(*args[r - 1][2:4]) if r > 0 else (None, 0)      # the left neighbour's right range
+                rr = copy(*args[r + 1][0:2]) if r + 1 < P else (None, 0)
+                answers[r] = (rl[0], rl[1], rr[0], rr[1])
+            for t in {a[i].device for a in answers for i in (0, 2) if a[i] is not None and a[i].is_cuda}:
+                torch.cuda.current_stream(t).synchronize()    # the copies are read on the contexts' streams
+        elif kind == "halo_v":
+            bands = [{side: (s.velocity_band(side)[0] if ok else None)
+                      for side, ok in (("L", s.has_left), ("R", s.has_right))} for s in ranks]
+            for r, s in enumerate(ranks):
+                s.set_ghost_velocities("L", bands[r - 1]["R"] if r > 0 else None)
+                s.set_ghost_velocities("R", bands[r + 1]["L"] if r + 1 < P else None)
+        elif kind == "sum":
+            answers = [sum(args)] * P
+        elif kind == "sum_tensor":
+            total = sum(t.clone() for t in args)
+            for t in args:
+                t.copy_(total)
+                if t.is_cuda:                                 # consumed on the context's stream
+                    torch.cuda.current_stream(t.device).synchronize()
         else:
-            sent = [s.phase_forces() for s in solvers]
-        exchange_and_advance(sent, True)
-        recut_if_due()
+            raise RuntimeError(f"unknown request {kind!r}")
 
 
 def gather_by_pid(solvers, name, n_global):

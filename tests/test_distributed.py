@@ -143,7 +143,7 @@ def test_local_slabs_match_single_domain(world, which):
     sd = _slab_scenes()[which]
     steps = 25
     ref, n = _single_domain(sd, steps)
-    solvers = [SlabSolver(sd, r, world, device=0) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, check_every=1) for r in range(world)]
     run_local_slabs(solvers, 1, initialize=True)
     run_local_slabs(solvers, steps)
     x = gather_by_pid(solvers, "x", n)
@@ -172,7 +172,7 @@ def test_local_slabs_restart_from_a_state(which):
     solver.step(12)
     ref = scenes.ps_by_pid(ps, "x")
     ps.close()
-    solvers = [SlabSolver(sd, r, 3, device=0, state=state) for r in range(3)]
+    solvers = [SlabSolver(sd, r, 3, device=0, check_every=1, state=state) for r in range(3)]
     run_local_slabs(solvers, 0, initialize=True)
     assert sum(s.owned_range[1] for s in solvers) == n
     run_local_slabs(solvers, 12)
@@ -219,7 +219,7 @@ def test_restart_with_dynamic_bodies_keeps_the_rest_centre_of_mass(tmp_path):
     ps2.close()
     assert scenes.rel_l2(x2, ref) <= 2e-6 and scenes.rel_l2(x2[rigid], ref[rigid]) <= 2e-6
     # two slabs, restarted
-    solvers = [SlabSolver(sd, r, 2, device=0, state=state) for r in range(2)]
+    solvers = [SlabSolver(sd, r, 2, device=0, check_every=1, state=state) for r in range(2)]
     run_local_slabs(solvers, 0, initialize=True)
     for s in solvers:
         got = s.ps.rigid_rest_cm.to_numpy()
@@ -239,7 +239,7 @@ def test_slab_rank_checkpoint_does_not_trip_over_consumed_accelerations(tmp_path
     refused; save_state() of that rank's ParticleSystem must still write a checkpoint (the field is dead across steps)."""
     from sph_taichi_amd.distributed import SlabSolver, run_local_slabs
     sd = _slab_scenes()[0]
-    solvers = [SlabSolver(sd, r, 2, device=0) for r in range(2)]
+    solvers = [SlabSolver(sd, r, 2, device=0, check_every=1) for r in range(2)]
     run_local_slabs(solvers, 0, initialize=True)
     run_local_slabs(solvers, 3)
     ck = str(tmp_path / "rank0.npz")
@@ -258,7 +258,7 @@ def test_layer_offsets_of_an_empty_record_set_are_zero():
     import ctypes as C
     from sph_taichi_amd.distributed import SlabSolver, run_local_slabs
     sd = _slab_scenes()[0]
-    solvers = [SlabSolver(sd, r, 2, device=0) for r in range(2)]
+    solvers = [SlabSolver(sd, r, 2, device=0, check_every=1) for r in range(2)]
     run_local_slabs(solvers, 0, initialize=True)
     run_local_slabs(solvers, 2)
     s = solvers[0]
@@ -281,7 +281,7 @@ def test_interior_accelerations_are_refused_while_they_are_not_materialised():
     from sph_taichi_amd import _lib
     from sph_taichi_amd.distributed import SlabSolver, run_local_slabs
     sd = _slab_scenes()[0]
-    solvers = [SlabSolver(sd, r, 2, device=0) for r in range(2)]
+    solvers = [SlabSolver(sd, r, 2, device=0, check_every=1) for r in range(2)]
     run_local_slabs(solvers, 0, initialize=True)
     run_local_slabs(solvers, 3)
     ps = solvers[0].ps
@@ -329,6 +329,88 @@ def test_plan_recut_moves_one_layer_towards_balance():
     assert plan_recut(list(slab_cuts(hist, 3, min_width=3)), hist, 3, 2) == list(slab_cuts(hist, 3, min_width=3))
 
 
+def test_lockstep_server_answers_the_four_request_kinds():
+    """`serve_lockstep` alone (CPU, stub ranks): what each rank is sent back for ("records", packed), ("halo_v", None),
+    ("sum", float) and ("sum_tensor", tensor), the orderings the send buffers need -- every context synchronised before a
+    range is handed over, nobody resumed before everybody has posted, and a rank that packs into its send buffers again
+    as soon as it is resumed (initialise does) does not change what its neighbours receive -- and ranks that diverge."""
+    import torch
+    from sph_taichi_amd.distributed import serve_lockstep, RECORD_BYTES
+    P, log = 3, []
+
+    class Ctx:
+        def __init__(self, r):
+            self.r = r
+
+        def sync(self):
+            log.append(("sync", self.r))
+
+    class Rank:
+        def __init__(self, r):
+            self.r, self.ps, self.has_left, self.has_right = r, Ctx(r), r > 0, r < P - 1
+            self.got, self.ghost_v = {}, {}
+            # send buffers larger than what is sent: 1 + r records of value 10 + r to the left, 2 + r of 100 + r to the right
+            self.send = {"L": torch.full((8 * RECORD_BYTES,), 10 + r, dtype=torch.uint8),
+                         "R": torch.full((8 * RECORD_BYTES,), 100 + r, dtype=torch.uint8)}
+
+        def velocity_band(self, side):
+            assert (side == "L" and self.has_left) or (side == "R" and self.has_right), "a band towards no neighbour"
+            log.append(("band", self.r))
+            return f"band{side}{self.r}", 1
+
+        def set_ghost_velocities(self, side, buf):
+            self.ghost_v[side] = buf
+
+        def protocol(self):
+            r = self.r
+            requests = (("records", (self.send["L"], 1 + r, self.send["R"], 2 + r)), ("halo_v", None),
+                        ("sum", (1e16, 1.0, -1e16)[r]),                    # only ((0 + a0) + a1) + a2 gives 0.0
+                        ("sum_tensor", torch.tensor([(1e16, 1.0, -1e16)[r], 1.0], dtype=torch.float64)),
+                        ("sum_tensor", torch.tensor([r + 1, 10 * (r + 1)], dtype=torch.int64)))
+            for k, (kind, arg) in enumerate(requests):
+                log.append(("post", r, k))
+                answer = yield (kind, arg)
+                log.append(("resume", r, k))
+                if kind == "records":                         # the next pack, before the next rank is resumed
+                    self.send["L"].fill_(255)
+                    self.send["R"].fill_(255)
+                self.got.setdefault(kind, []).append(arg if kind == "sum_tensor" else answer)
+
+    ranks = [Rank(r) for r in range(P)]
+    serve_lockstep(ranks, [s.protocol() for s in ranks])
+    # records: (left neighbour's RIGHT range, right neighbour's LEFT range), nothing at the domain ends
+    for r, s in enumerate(ranks):
+        rl, nl, rr, nr = s.got["records"][0]
+        assert (nl, nr) == (2 + r - 1 if r > 0 else 0, 1 + r + 1 if r + 1 < P else 0)
+        assert (rl is None) == (r == 0) and (rr is None) == (r == P - 1)
+        assert r == 0 or rl.tolist() == [100 + r - 1] * (nl * RECORD_BYTES), "not what the left neighbour packed BEFORE it ran on"
+        assert r == P - 1 or rr.tolist() == [10 + r + 1] * (nr * RECORD_BYTES)
+    assert [s.ghost_v for s in ranks] == [{"L": None, "R": "bandL1"}, {"L": "bandR0", "R": "bandL2"}, {"L": "bandR1", "R": None}]
+    assert [s.got["sum"][0] for s in ranks] == [0.0] * P                        # in rank order, the same on every rank
+    for s in ranks:                                                              # written into each rank's OWN tensor
+        f64, i64 = s.got["sum_tensor"]
+        assert f64.dtype == torch.float64 and f64.tolist() == [0.0, 3.0]
+        assert i64.dtype == torch.int64 and i64.tolist() == [6, 60]
+    assert len({id(s.got["sum_tensor"][0]) for s in ranks}) == P
+    # lock-step, per request k: all P ranks have posted it (in rank order) before the server touches anything -- the syncs
+    # of ALL contexts for "records", the bands for "halo_v" -- and only then is anybody resumed (in rank order)
+    for k, kind in enumerate(["records", "halo_v", "sum", "sum_tensor", "sum_tensor"]):
+        posted, resumed = ([log.index((what, r, k)) for r in range(P)] for what in ("post", "resume"))
+        assert posted == sorted(posted) and resumed == sorted(resumed) and posted[-1] < resumed[0]
+        assert log[posted[-1] + 1:resumed[0]] == {"records": [("sync", r) for r in range(P)],
+                                                  "halo_v": [("band", 0), ("band", 1), ("band", 1), ("band", 2)]}.get(kind, [])
+    assert len(log) == 2 * P * 5 + P + 4
+
+    def posts(*kinds):
+        for kind in kinds:
+            yield (kind, 1.0 if kind == "sum" else None)
+
+    with pytest.raises(RuntimeError, match="ranks diverged"):
+        serve_lockstep(ranks[:2], [posts("sum", "sum"), posts("sum", "halo_v")])
+    with pytest.raises(RuntimeError, match="ranks diverged"):                    # one rank is done, the other still asks
+        serve_lockstep(ranks[:2], [posts("sum"), posts("sum", "sum")])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["fluid-2", "fluid-3", "bodies-2", "dfsph-2"])
 def test_local_slabs_recut(case, tmp_path):
@@ -353,7 +435,7 @@ def test_local_slabs_recut(case, tmp_path):
     # skewed start: every interior cut 4 layers right of the balanced one (clipped so that every slab is valid)
     cuts = [0] + [min(c + 4, nx - (world - i) * (halo + 1)) for i, c in enumerate(balanced[1:-1], 1)] + [nx]
     assert cuts != balanced and filled.size > 0
-    solvers = [SlabSolver(sd, r, world, device=0, cuts=cuts, recut_every=2) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, check_every=1, cuts=cuts, recut_every=2) for r in range(world)]
     run_local_slabs(solvers, 1, initialize=True)
     run_local_slabs(solvers, steps)
     assert sum(s.stats.get("recuts", 0) for s in solvers) >= 2, "no cut moved"
@@ -393,7 +475,7 @@ def test_a_slab_rank_beyond_the_32_bit_list_offsets_is_refused():
     from sph_taichi_amd import _lib
     sd = _slab_scenes()[0]
     n = scenes.build(sd)[1].particle_max_num
-    s = SlabSolver(sd, 0, 1, device=0, capacity_factor=(1 << 24) / n + 64.0)
+    s = SlabSolver(sd, 0, 1, device=0, check_every=1, capacity_factor=(1 << 24) / n + 64.0)
     assert s.capacity > (1 << 24)
     run_local_slabs([s], 1, initialize=True)
     with pytest.raises(_lib.SphError, match="more slabs"):
@@ -410,7 +492,7 @@ def test_local_slabs_shape_matched_bodies(world, tmp_path):
     sd = scenes.fluid_with_rigid_bodies(str(tmp_path / "cube.obj"), fluid_velocity=(0.8, -1.0, 0.0))
     steps = 40
     ref, n = _single_domain(sd, steps)
-    solvers = [SlabSolver(sd, r, world, device=0) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, check_every=1) for r in range(world)]
     assert solvers[0].halo == 3 and solvers[0].dynamic_bodies == [1, 2]
     cfg, sc = scenes.build(sd)
     layers = (sc.arrays["x"][sc.arrays["object_id"] == 2, 0] / np.float32(0.04)).astype(int)
@@ -455,7 +537,7 @@ def test_local_slabs_dfsph(world):
     ref = {k: scenes.ps_by_pid(ps, k) for k in ("x", "v")}
     ps.close()
     assert sum(a + b for a, b in its) > 0, "the solvers never iterated: the scene does not test the refresh"
-    solvers = [SlabSolver(sd, r, world, device=0) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, check_every=1) for r in range(world)]
     run_local_slabs(solvers, 1, initialize=True)
     got = []
     for _ in range(steps):
@@ -491,7 +573,7 @@ def test_local_slabs_dfsph_with_dynamic_solids(world, tmp_path):
     solver.initialize(); solver.step(steps)
     ref = {k: scenes.ps_by_pid(ps, k) for k in ("x", "v")}
     ps.close()
-    solvers = [SlabSolver(sd, r, world, device=0) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, check_every=1) for r in range(world)]
     assert solvers[0].halo == 3 and solvers[0].dynamic_bodies == [1, 2]
     run_local_slabs(solvers, 1, initialize=True)
     run_local_slabs(solvers, steps)
@@ -777,7 +859,7 @@ def test_conservation_guard_raises_when_a_particle_outruns_the_halo():
     from sph_taichi_amd.distributed import SlabSolver, run_local_slabs
     sd = scenes.fluid_only(counts=(20, 10, 8), start=(0.1, 0.1, 0.1), velocity=(1.5, -1.0, 0.0))
     sd["Configuration"]["timeStepSize"] = 0.05      # 1.5 m/s * 0.05 s = 0.075 m = almost two cell layers (h = 0.04) per step
-    solvers = [SlabSolver(sd, r, 2, device=0) for r in range(2)]
+    solvers = [SlabSolver(sd, r, 2, device=0, check_every=1) for r in range(2)]
     run_local_slabs(solvers, 0, initialize=True)
     with pytest.raises(RuntimeError, match="conservation"):
         run_local_slabs(solvers, 6)

@@ -118,7 +118,7 @@ def test_c4_eight_logical_slabs_vs_the_oracle_trajectory():
     nx = len(hist)
     start = [0] + [min(c + 3, nx - (world - i) * (halo + 1)) for i, c in enumerate(bal[1:-1], 1)] + [nx]   # three layers off balance
     assert start != bal
-    solvers = [SlabSolver(sd, r, world, device=0, cuts=start, recut_every=3, state=state) for r in range(world)]
+    solvers = [SlabSolver(sd, r, world, device=0, cuts=start, recut_every=3, check_every=1, state=state) for r in range(world)]
     run_local_slabs(solvers, 0, initialize=True)
     owned0 = [int(s.owned_range[1]) for s in solvers]
     assert sum(owned0) == N_C4

@@ -4,7 +4,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from sph_taichi_amd import ParticleSystem, SimConfig, _lib
-from sph_taichi_amd.distributed import SlabSolver, slab_bench_scene, LocalTransport
+from sph_taichi_amd.distributed import SlabSolver, slab_bench_scene
 import copy
 
 sd, n = slab_bench_scene(1)
@@ -15,8 +15,11 @@ print(f"plain sph_step            : {(t1 - t0) * 10:.3f} ms/step  ({n} particles
 ps.close()
 
 class NoTransport:
-    def start_counts(self, a, b): self._pending = None
+    stream_ordered = False
+    def start_counts(self, a, b): pass
+    def resolve_counts(self): pass
     def exchange(self, sL, nL, sR, nR, alloc): return None, 0, None, 0
+    def swap(self, sL, sR, rL, rR): pass
     def all_reduce_sum(self, t): return t
 s = SlabSolver(sd, 0, 1, device=0)
 s.attach(NoTransport()); s.initialize(); s.step(10); s.ps.sync()
