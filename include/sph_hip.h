@@ -480,6 +480,58 @@ int32_t sph_render_download(SphContext* ctx, uint8_t* rgb, size_t bytes);   /* u
 /* f32 [height, width]: distance along the view direction of what the pixel shows, +inf where nothing was drawn; synchronises */
 int32_t sph_render_download_depth(SphContext* ctx, float* depth, size_t bytes);
 
+/* ======================================================================================
+ * Kinematic rigid bodies (no reference counterpart: the reference's solids are frozen or shape-matched): a
+ * NON-dynamic solid object whose motion the caller prescribes -- a piston, a flap, a stirrer, a gate.
+ *
+ * Motion of a registered object, with tau = clamp(t, start_time, end_time) - start_time and t the context's clock:
+ *     d(tau) = lin_vel tau + osc_amplitude (sin(2 pi osc_frequency tau + osc_phase) - sin(osc_phase))
+ *     R(tau) = rotation about ang_vel / |ang_vel| by |ang_vel| tau (Rodrigues; identity when ang_vel = 0)
+ *     x(t)   = pivot + d + R (x_0 - pivot)
+ *     v(t)   = d'(tau) + ang_vel x (x - pivot - d);   v = 0 for t outside [start_time, end_time]
+ * The CLOCK is an f64 held by the context: 0 at sph_create, advanced by the current dt at the end of every step of
+ * sph_step / sph_dfsph_step (so sph_set_dt between two calls is honoured), read and set with sph_get_time /
+ * sph_set_time.  It advances whether or not a motion is registered.
+ * WHERE IN THE STEP: while motions are registered, every step of sph_step / sph_dfsph_step ends -- behind the substep,
+ * the dynamic bodies' solve and the fluid wall pass, i.e. where the reference moves its bodies (sph_base.py:263-271)
+ * -- by placing every registered object at the pose of the step's END time: one launch for all objects, the pose
+ * evaluated on the host in f64, rounded to f32 and passed by value.  During step k the fluid therefore sees the body
+ * at pose(t_{k-1}) with velocity(t_{k-1}).  Nothing synchronises; sph_step(n) still only enqueues.  With no motion
+ * registered the two step calls enqueue exactly what they enqueue without this section.
+ * The kernel writes x and v of the object's particles (from the pid-indexed x_0) and nothing else; what it writes
+ * does not depend on particle order or scheduling (csrc/sph_integrate.hip states the f32 arithmetic).
+ * CONTAINMENT: before a step is enqueued the object's rest bounding box (eight corners, f64) is carried through the
+ * step's end pose; unless all of it lies inside [padding, domain_size - padding] the call returns SPH_E_INVALID with the
+ * object and the step named in sph_last_error -- that step and the later ones are not enqueued, the earlier steps of
+ * the call stand, the clock stays at the last enqueued step's end.  sph_kinematic_apply checks the same way.
+ * BOUNDARY VOLUMES: a kinematic object keeps the m_V that compute_static_boundary_volume (sph_base.py:91-98) gave it
+ * at initialize().  Rigid motion preserves the distances inside the object, so that is exact while the object stays
+ * a support radius away from every OTHER solid; sph_compute_boundary_volume(ctx, 0) refreshes all static volumes on
+ * demand (there is no per-step refresh).
+ * SPH_E_INVALID: object id outside [0, n_objects) or without particles, an object with dynamic (or fluid)
+ * particles, n > SPH_MAX_KINEMATIC, an id given twice, a non-finite field (end_time may be +inf), end_time <
+ * start_time, for sph_kinematic_apply an R that is not orthonormal to 1e-4.  Single-domain contexts only: a slab rank
+ * answers SPH_E_STATE.
+ * ==================================================================================== */
+#define SPH_MAX_KINEMATIC 8
+typedef struct SphKinematicMotion {
+    int32_t object_id;
+    float pivot[3];
+    double lin_vel[3], ang_vel[3], osc_amplitude[3], osc_frequency, osc_phase, start_time, end_time;
+} SphKinematicMotion;
+typedef struct SphBodyPose {
+    int32_t object_id;
+    float R[9];         /* row-major */
+    float pivot[3], origin[3], lin_vel[3], ang_vel[3];   /* x = origin + R (x_0 - pivot), v = lin_vel + ang_vel x (x - origin) */
+} SphBodyPose;
+/* Replace the set of registered motions (n = 0 clears; n <= SPH_MAX_KINEMATIC).  Reads the objects' rest bounding boxes from
+ * one download of x_0 the first time (synchronises then). */
+int32_t sph_kinematic_set(SphContext* ctx, const SphKinematicMotion* motions, int32_t n);
+/* Stand-alone: place n objects at the given poses now (enqueues; trajectories scripted by the caller). */
+int32_t sph_kinematic_apply(SphContext* ctx, const SphBodyPose* poses, int32_t n);
+int32_t sph_get_time(SphContext* ctx, double* t);
+int32_t sph_set_time(SphContext* ctx, double t);
+
 #ifdef __cplusplus
 }
 #endif

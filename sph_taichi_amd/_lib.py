@@ -60,6 +60,22 @@ class SphRenderParams(C.Structure):
 
 
 RENDER_MAX_INVISIBLE = 32
+_D3 = C.c_double * 3
+
+
+class SphKinematicMotion(C.Structure):
+    """Mirror of `struct SphKinematicMotion` (include/sph_hip.h)."""
+    _fields_ = [("object_id", C.c_int32), ("pivot", _F3), ("lin_vel", _D3), ("ang_vel", _D3), ("osc_amplitude", _D3),
+                ("osc_frequency", C.c_double), ("osc_phase", C.c_double), ("start_time", C.c_double), ("end_time", C.c_double)]
+
+
+class SphBodyPose(C.Structure):
+    """Mirror of `struct SphBodyPose` (include/sph_hip.h)."""
+    _fields_ = [("object_id", C.c_int32), ("R", C.c_float * 9), ("pivot", _F3), ("origin", _F3), ("lin_vel", _F3),
+                ("ang_vel", _F3)]
+
+
+MAX_KINEMATIC = 8
 
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
@@ -166,6 +182,10 @@ SYMBOLS = [
     ("sph_render_frame", C.c_int32, [_ctx]),
     ("sph_render_download", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
     ("sph_render_download_depth", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_kinematic_set", C.c_int32, [_ctx, C.POINTER(SphKinematicMotion), C.c_int32]),
+    ("sph_kinematic_apply", C.c_int32, [_ctx, C.POINTER(SphBodyPose), C.c_int32]),
+    ("sph_get_time", C.c_int32, [_ctx, C.POINTER(C.c_double)]),
+    ("sph_set_time", C.c_int32, [_ctx, C.c_double]),
 ]
 
 _LIB = None

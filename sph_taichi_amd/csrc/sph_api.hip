@@ -1,7 +1,10 @@
 // sph_api.hip -- the extern "C" surface declared in include/sph_hip.h: context
 // lifetime, field upload/download, one entry point per reference kernel, and
 // sph_step = SPHBase.step() (sph_base.py:263-271) looped on the device.
+#include <math.h>
 #include <sched.h>
+#include <new>
+#include <vector>
 #include "sph_internal.h"
 
 #define SCAN_TILE 2048
@@ -93,6 +96,158 @@ int sph_check_device_flags(SphContext* c) {
 
 // SPH_OPT_KERNEL_VARIANT / the SPH_KERNEL_VARIANT environment default: GAT_LDS and GAT_LDS4 exclude each other
 static bool variant_mask_ok(int v) { return (v & (SPH_VAR_GAT_LDS | SPH_VAR_GAT_LDS4)) != (SPH_VAR_GAT_LDS | SPH_VAR_GAT_LDS4); }
+
+// ---- kinematic bodies: host side (sph_hip.h, last section) -------------------------------------------------------------
+// pose of a registered motion at time t, in f64: R (row-major), c = pivot + d, u = d', w = ang_vel (u = w = 0 outside
+// [start_time, end_time]).  sph_taichi_amd/motion.py: pose() is the same formula in numpy.
+struct KinPose64 { double R[9], c[3], u[3], w[3]; };
+static void kin_pose(const SphKinematicMotion& m, double t, KinPose64* out) {
+    const double tc = t < m.start_time ? m.start_time : (t > m.end_time ? m.end_time : t);
+    const double tau = tc - m.start_time;
+    const bool active = t >= m.start_time && t <= m.end_time;
+    const double two_pi = 6.283185307179586476925286766559;
+    const double arg = two_pi * m.osc_frequency * tau + m.osc_phase;
+    const double s = sin(arg) - sin(m.osc_phase), ds = two_pi * m.osc_frequency * cos(arg);
+    for (int a = 0; a < 3; ++a) {
+        out->c[a] = (double)m.pivot[a] + (m.lin_vel[a] * tau + m.osc_amplitude[a] * s);
+        out->u[a] = active ? m.lin_vel[a] + m.osc_amplitude[a] * ds : 0.0;
+        out->w[a] = active ? m.ang_vel[a] : 0.0;
+    }
+    const double wn = sqrt(m.ang_vel[0] * m.ang_vel[0] + m.ang_vel[1] * m.ang_vel[1] + m.ang_vel[2] * m.ang_vel[2]);
+    double* R = out->R;
+    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    if (wn > 0.0) {   // Rodrigues: R = I + sin(th) K + (1 - cos(th)) K^2, K = [k]_x
+        const double k[3] = {m.ang_vel[0] / wn, m.ang_vel[1] / wn, m.ang_vel[2] / wn};
+        const double th = wn * tau, sn = sin(th), cs1 = 1.0 - cos(th);
+        const double K[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double kk = 0.0;
+                for (int l = 0; l < 3; ++l) kk += K[3 * i + l] * K[3 * l + j];
+                R[3 * i + j] += sn * K[3 * i + j] + cs1 * kk;
+            }
+    }
+}
+
+// per object: particle counts and the bounding box of the rest positions, from one download of (x_0, flags); synchronises
+static int sph_obj_info(SphContext* c) {
+    if (c->obj_info_valid) return 0;
+    const int no = c->p.n_objects;
+    if (!c->obj_info) {
+        c->obj_info = new (std::nothrow) SphContext::ObjInfo[no > 0 ? no : 1];
+        if (!c->obj_info) return sph_fail(c, SPH_E_NOMEM, "kinematic bodies: out of host memory");
+    }
+    for (int o = 0; o < no; ++o) {
+        c->obj_info[o].n = c->obj_info[o].n_static = 0;
+        for (int a = 0; a < 3; ++a) { c->obj_info[o].lo[a] = INFINITY; c->obj_info[o].hi[a] = -INFINITY; }
+    }
+    if (c->N > 0) {
+        std::vector<float> rec;
+        try { rec.resize((size_t)c->N * 4); } catch (...) { return sph_fail(c, SPH_E_NOMEM, "kinematic bodies: out of host memory"); }
+        int rc = sphk_rest_records(c, reinterpret_cast<float4*>(c->stage));   // (the staging buffer holds 16 B per record of capacity)
+        if (rc) return rc;
+        SPH_HIP(c, hipMemcpyAsync(rec.data(), c->stage, rec.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        SPH_HIP(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < c->N; ++i) {
+            int fl;
+            memcpy(&fl, &rec[4 * (size_t)i + 3], sizeof(int));
+            const int o = (int)((unsigned)fl >> 9);
+            if (o >= no) continue;
+            SphContext::ObjInfo& I = c->obj_info[o];
+            I.n += 1;
+            I.n_static += (fl & 0x1FF) == 0 ? 1 : 0;
+            for (int a = 0; a < 3; ++a) {
+                const double v = (double)rec[4 * (size_t)i + a];
+                I.lo[a] = v < I.lo[a] ? v : I.lo[a];
+                I.hi[a] = v > I.hi[a] ? v : I.hi[a];
+            }
+        }
+    }
+    c->obj_info_valid = true;
+    return 0;
+}
+
+// may this object be moved kinematically?  (0, or SPH_E_INVALID with the message set)
+static int kin_check_object(SphContext* c, const char* who, int object_id) {
+    if (object_id < 0 || object_id >= c->p.n_objects) {
+        snprintf(c->err, sizeof(c->err), "%s: object id %d is outside [0, n_objects = %d)", who, object_id, c->p.n_objects);
+        return SPH_E_INVALID;
+    }
+    const SphContext::ObjInfo& I = c->obj_info[object_id];
+    if (I.n == 0) {
+        snprintf(c->err, sizeof(c->err), "%s: object %d has no particles", who, object_id);
+        return SPH_E_INVALID;
+    }
+    if (I.n_static != I.n) {
+        snprintf(c->err, sizeof(c->err), "%s: object %d has %d dynamic or fluid particles: only a non-dynamic solid can be kinematic", who,
+                 object_id, I.n - I.n_static);
+        return SPH_E_INVALID;
+    }
+    return 0;
+}
+
+// the object's rest box carried through x = c + R (x_0 - pivot): do all eight corners lie inside [padding, domain - padding]?
+static bool kin_contained(const SphContext* c, int object_id, const double R[9], const double pivot[3], const double origin[3]) {
+    const SphContext::ObjInfo& I = c->obj_info[object_id];
+    for (int k = 0; k < 8; ++k) {
+        const double q[3] = {((k & 1) ? I.hi[0] : I.lo[0]) - pivot[0], ((k & 2) ? I.hi[1] : I.lo[1]) - pivot[1],
+                             ((k & 4) ? I.hi[2] : I.lo[2]) - pivot[2]};
+        for (int a = 0; a < 3; ++a) {
+            const double x = origin[a] + (R[3 * a] * q[0] + R[3 * a + 1] * q[1] + R[3 * a + 2] * q[2]);
+            if (!(x >= (double)c->p.padding && x <= (double)c->p.domain_size[a] - (double)c->p.padding)) return false;
+        }
+    }
+    return true;
+}
+
+// poses of all registered motions at time t, f64 -> f32, for the kernel
+static void kin_poses_at(const SphContext* c, double t, KinPoses* P) {
+    P->n = c->n_kin;
+    for (int k = 0; k < SPH_MAX_KINEMATIC; ++k) P->id[k] = -1;
+    for (int k = 0; k < c->n_kin; ++k) {
+        const SphKinematicMotion& m = c->kin[k];
+        KinPose64 q;
+        kin_pose(m, t, &q);
+        P->id[k] = m.object_id;
+        for (int j = 0; j < 9; ++j) P->R[k][j] = (float)q.R[j];
+        for (int a = 0; a < 3; ++a) {
+            P->pivot[k][a] = m.pivot[a];
+            P->origin[k][a] = (float)q.c[a];
+            P->lin[k][a] = (float)q.u[a];
+            P->ang[k][a] = (float)q.w[a];
+        }
+    }
+}
+
+// Containment, before anything of a step call is enqueued: *n_run = how many of the call's n_steps steps may run -- all of
+// them (returns 0), or those before the first step at whose end a registered object would not lie inside
+// [padding, domain - padding] (returns SPH_E_INVALID with the message set; the caller enqueues *n_run steps and hands the code on).
+static int kin_admit(SphContext* c, int n_steps, int* n_run) {
+    *n_run = 0;
+    if (!c->obj_info_valid) {   // x_0 / ids / flags were uploaded since sph_kinematic_set (a restart): look again
+        int rc = sph_obj_info(c);
+        for (int k = 0; k < c->n_kin && !rc; ++k) rc = kin_check_object(c, "kinematic step", c->kin[k].object_id);
+        if (rc) return rc;
+    }
+    double t = c->sim_time;
+    for (int it = 0; it < n_steps; ++it) {
+        t += (double)c->p.dt;   // (the same additions the step loop makes)
+        for (int k = 0; k < c->n_kin; ++k) {
+            const SphKinematicMotion& m = c->kin[k];
+            KinPose64 q;
+            kin_pose(m, t, &q);
+            const double pivot[3] = {(double)m.pivot[0], (double)m.pivot[1], (double)m.pivot[2]};
+            if (!kin_contained(c, m.object_id, q.R, pivot, q.c)) {
+                snprintf(c->err, sizeof(c->err), "kinematic object %d would leave [padding, domain - padding] at the end of step %d of this call "
+                         "(t = %.9g): that step and the later ones were not enqueued, %d step(s) were", m.object_id, it, t, it);
+                *n_run = it;
+                return SPH_E_INVALID;
+            }
+        }
+    }
+    *n_run = n_steps;
+    return 0;
+}
 
 extern "C" {
 
@@ -266,6 +421,7 @@ int32_t sph_destroy(SphContext* c) {
                     c->rigid_rest_cm, c->dyn_list, c->dyn_count, c->acc_fx, c->rigid_part, c->rigid_R, c->df_err, c->df_part, c->df_bpart, c->stage, c->glist, c->gcnt, c->brick_list, c->brick_count, c->brick_list2, c->brick_count2, c->brick_rec};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     sph_render_release(c);
+    delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
@@ -366,6 +522,7 @@ int32_t sph_set_particle_count(SphContext* c, int32_t n) {
     if (!c || n < 0 || n > c->cap) return sph_fail(c, SPH_E_INVALID, "particle count out of range");
     c->N = n;
     c->n_dyn_host = -1;
+    c->obj_info_valid = false;
     sph_forget_pure_fluid(c);
     sphd_set_changed(c->dv);
     c->have_keys = c->have_prefix = false;
@@ -402,6 +559,8 @@ int32_t sph_upload(SphContext* c, int32_t field, const void* host, size_t bytes)
     if (field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC || field == SPH_F_DENSITY) c->n_dyn_host = -1;  // (density: the scale of the rigid sums)
     if (field == SPH_F_MATERIAL || field == SPH_F_M || field == SPH_F_M_V) c->uniform_state = -1;
     if (field == SPH_F_X) c->have_keys = c->have_prefix = false;
+    if (field == SPH_F_X_0 || field == SPH_F_OBJECT_ID || field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC || field == SPH_F_PID)
+        c->obj_info_valid = false;
     return 0;
 }
 
@@ -721,8 +880,14 @@ int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int
     if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) return sph_fail(c, SPH_E_INVALID, "sph_step: bad arguments");
     int rc = refresh_dyn(c);
     if (rc) return rc;
+    int kin_rc = 0;
+    if (c->n_kin > 0) {   // registered kinematic bodies: only the steps that keep them inside the domain are enqueued
+        kin_rc = kin_admit(c, n_steps, &n_steps);
+        if (kin_rc && kin_rc != SPH_E_INVALID) return kin_rc;
+    }
     if (n_steps > 0) c->acc_partial = false;   // the call's last step writes every acceleration out
     for (int it = 0; it < n_steps; ++it) {
+        const double t_end = c->sim_time + (double)c->p.dt;
         hipEvent_t* ev = nullptr;
         const bool timing = sph_timed_step(c);  // SPH_OPT_TIMING k: every k-th step carries the five events
         if (timing) {
@@ -740,9 +905,16 @@ int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int
         rc = step_sweeps(c, ev, dynamic_ids, n_dynamic);
         c->skip_acc = 0;
         if (rc) return rc;
+        if (c->n_kin > 0) {   // registered bodies -> pose(t_end)
+            KinPoses kin;
+            kin_poses_at(c, t_end, &kin);
+            rc = sphk_kinematic_apply(c, kin);
+            if (rc) return rc;
+        }
+        c->sim_time = t_end;
         if (timing) { SPH_HIP(c, hipEventRecord(ev[4], c->stream)); c->ev_used++; }
     }
-    return 0;
+    return kin_rc;
 }
 
 // ---- multi-GPU slab support ---------------------------------------------------
@@ -1272,8 +1444,14 @@ int32_t sph_dfsph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_id
     if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) return sph_fail(c, SPH_E_INVALID, "sph_dfsph_step: bad arguments");
     int rc = refresh_dyn(c);
     if (rc) return rc;
+    int kin_rc = 0;
+    if (c->n_kin > 0) {   // registered kinematic bodies: only the steps that keep them inside the domain are enqueued
+        kin_rc = kin_admit(c, n_steps, &n_steps);
+        if (kin_rc && kin_rc != SPH_E_INVALID) return kin_rc;
+    }
     if (n_steps > 0) c->acc_partial = false;
     for (int it = 0; it < n_steps; ++it) {
+        const double t_end = c->sim_time + (double)c->p.dt;
         hipEvent_t* ev = nullptr;
         const bool timing = sph_timed_step(c);  // SPH_OPT_TIMING k: every k-th step carries the five events
         if (timing) {
@@ -1301,10 +1479,17 @@ int32_t sph_dfsph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_id
         rc = sphk_df_advect(c, true);                                // advect + enforce_boundary_3D(fluid)
         if (rc) return rc;
         if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }  // solve_rigid_body()  sph_base.py:247-260
+        if (c->n_kin > 0) {   // registered bodies -> pose(t_end)
+            KinPoses kin;
+            kin_poses_at(c, t_end, &kin);
+            rc = sphk_kinematic_apply(c, kin);
+            if (rc) return rc;
+        }
+        c->sim_time = t_end;
         if (timing) { SPH_HIP(c, hipEventRecord(ev[4], c->stream)); c->ev_used++; }
         c->df_stats.steps++;
     }
-    return 0;
+    return kin_rc;
 }
 
 #ifdef SPH_PROFILE
@@ -1317,6 +1502,105 @@ int32_t sph_profile_read(SphContext* c, void* host, size_t bytes) {
     return 0;
 }
 #endif
+
+// ---- kinematic bodies ----------------------------------------------------------------------------------------------------
+static bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+static bool finite3f(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+
+int32_t sph_kinematic_set(SphContext* c, const SphKinematicMotion* motions, int32_t n) {
+    ENTER(c);
+    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_kinematic_set: this context is a slab rank; kinematic bodies exist on single-domain contexts only");
+    if (n < 0 || n > SPH_MAX_KINEMATIC || (n > 0 && !motions)) return sph_fail(c, SPH_E_INVALID, "sph_kinematic_set: n must be in [0, SPH_MAX_KINEMATIC] (and motions non-null)");
+    for (int k = 0; k < n; ++k) {
+        const SphKinematicMotion& m = motions[k];
+        if (!finite3f(m.pivot) || !finite3(m.lin_vel) || !finite3(m.ang_vel) || !finite3(m.osc_amplitude) || !isfinite(m.osc_frequency) ||
+            !isfinite(m.osc_phase) || !isfinite(m.start_time) || isnan(m.end_time) || m.end_time == -INFINITY) {
+            snprintf(c->err, sizeof(c->err), "sph_kinematic_set: motion %d (object %d) has a non-finite field", k, m.object_id);
+            return SPH_E_INVALID;
+        }
+        if (m.end_time < m.start_time) return sph_fail(c, SPH_E_INVALID, "sph_kinematic_set: end_time < start_time");
+        for (int j = 0; j < k; ++j)
+            if (motions[j].object_id == m.object_id) return sph_fail(c, SPH_E_INVALID, "sph_kinematic_set: an object id is given twice");
+    }
+    if (n > 0) {
+        int rc = sph_obj_info(c);
+        for (int k = 0; k < n && !rc; ++k) rc = kin_check_object(c, "sph_kinematic_set", motions[k].object_id);
+        if (rc) return rc;
+    }
+    c->n_kin = n;
+    for (int k = 0; k < n; ++k) c->kin[k] = motions[k];
+    return 0;
+}
+
+int32_t sph_kinematic_apply(SphContext* c, const SphBodyPose* poses, int32_t n) {
+    ENTER(c);
+    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_kinematic_apply: this context is a slab rank; kinematic bodies exist on single-domain contexts only");
+    if (n < 0 || n > SPH_MAX_KINEMATIC || (n > 0 && !poses)) return sph_fail(c, SPH_E_INVALID, "sph_kinematic_apply: n must be in [0, SPH_MAX_KINEMATIC] (and poses non-null)");
+    if (n == 0) return 0;
+    for (int k = 0; k < n; ++k) {
+        const SphBodyPose& b = poses[k];
+        bool fin = finite3f(b.pivot) && finite3f(b.origin) && finite3f(b.lin_vel) && finite3f(b.ang_vel);
+        for (int j = 0; j < 9; ++j) fin = fin && isfinite(b.R[j]);
+        if (!fin) {
+            snprintf(c->err, sizeof(c->err), "sph_kinematic_apply: pose %d (object %d) has a non-finite field", k, b.object_id);
+            return SPH_E_INVALID;
+        }
+        for (int i = 0; i < 3; ++i)          // R R^T = I to 1e-4, det R = +1
+            for (int j = i; j < 3; ++j) {
+                double dot = 0.0;
+                for (int l = 0; l < 3; ++l) dot += (double)b.R[3 * i + l] * (double)b.R[3 * j + l];
+                if (fabs(dot - (i == j ? 1.0 : 0.0)) > 1e-4) {
+                    snprintf(c->err, sizeof(c->err), "sph_kinematic_apply: R of pose %d (object %d) is not orthonormal to 1e-4", k, b.object_id);
+                    return SPH_E_INVALID;
+                }
+            }
+        const double det = (double)b.R[0] * ((double)b.R[4] * b.R[8] - (double)b.R[5] * b.R[7]) - (double)b.R[1] * ((double)b.R[3] * b.R[8] - (double)b.R[5] * b.R[6]) +
+                           (double)b.R[2] * ((double)b.R[3] * b.R[7] - (double)b.R[4] * b.R[6]);
+        if (det < 0.0) {
+            snprintf(c->err, sizeof(c->err), "sph_kinematic_apply: R of pose %d (object %d) is a reflection (det = -1)", k, b.object_id);
+            return SPH_E_INVALID;
+        }
+        for (int j = 0; j < k; ++j)
+            if (poses[j].object_id == b.object_id) return sph_fail(c, SPH_E_INVALID, "sph_kinematic_apply: an object id is given twice");
+    }
+    int rc = sph_obj_info(c);
+    if (rc) return rc;
+    KinPoses P;
+    P.n = n;
+    for (int k = 0; k < SPH_MAX_KINEMATIC; ++k) P.id[k] = -1;
+    for (int k = 0; k < n; ++k) {
+        const SphBodyPose& b = poses[k];
+        rc = kin_check_object(c, "sph_kinematic_apply", b.object_id);
+        if (rc) return rc;
+        double R[9], pivot[3], origin[3];
+        for (int j = 0; j < 9; ++j) R[j] = (double)b.R[j];
+        for (int a = 0; a < 3; ++a) { pivot[a] = (double)b.pivot[a]; origin[a] = (double)b.origin[a]; }
+        if (!kin_contained(c, b.object_id, R, pivot, origin)) {
+            snprintf(c->err, sizeof(c->err), "sph_kinematic_apply: object %d would leave [padding, domain - padding]; nothing was enqueued", b.object_id);
+            return SPH_E_INVALID;
+        }
+        P.id[k] = b.object_id;
+        memcpy(P.R[k], b.R, sizeof(b.R));
+        memcpy(P.pivot[k], b.pivot, sizeof(b.pivot));
+        memcpy(P.origin[k], b.origin, sizeof(b.origin));
+        memcpy(P.lin[k], b.lin_vel, sizeof(b.lin_vel));
+        memcpy(P.ang[k], b.ang_vel, sizeof(b.ang_vel));
+    }
+    return sphk_kinematic_apply(c, P);
+}
+
+int32_t sph_get_time(SphContext* c, double* t) {
+    if (!c || !t) return SPH_E_INVALID;
+    *t = c->sim_time;
+    return 0;
+}
+
+int32_t sph_set_time(SphContext* c, double t) {
+    if (!c) return SPH_E_INVALID;
+    if (!isfinite(t)) return sph_fail(c, SPH_E_INVALID, "sph_set_time: the time must be finite");
+    c->sim_time = t;
+    return 0;
+}
 
 int32_t sph_slab_wait_pack(SphContext* c) {
     ENTER(c);

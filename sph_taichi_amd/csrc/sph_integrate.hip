@@ -865,6 +865,59 @@ __global__ __launch_bounds__(TPB) void k_build_dyn_list(DevView d, int* __restri
     }
 }
 
+// ---- kinematic bodies (sph_hip.h, last section) ---------------------------------------------------------------------
+// One launch places every registered object at its pose.  Form: a STREAM over all N records that reads vf (16 B per lane,
+// coalesced) and decides from vf.w -- "solid, not dynamic" and the object id in the table (at most SPH_MAX_KINEMATIC ids, a
+// wave-uniform loop over kernel arguments); only the lanes of a registered object go on to read aux.w (the persistent id), the
+// three words of x_0[pid] and xm, and to write xm and vf.  The alternative, a compacted list like the dynamic bodies', is
+// built inside the sort's scatter; this form leaves the sort alone and costs one read of vf (DESIGN.md 12 has the numbers).
+// One lane owns one particle and writes only that particle's records: no atomics, no hand-off, so the result depends on
+// neither the particle order nor the scheduling.
+//
+// The f32 arithmetic, operation by operation (R row-major, every operation rounded to nearest; the fused multiply-adds
+// are written out so that the compiler's contraction choice cannot change a bit):
+//     q_a = x_0[pid]_a - pivot_a                                        a = 0, 1, 2
+//     r_a = fma(R_a2, q_2, fma(R_a1, q_1, R_a0 * q_0))
+//     x_a = origin_a + r_a
+//     v_0 = lin_0 + fma(w_1, r_2, -(w_2 * r_1))    v_1 = lin_1 + fma(w_2, r_0, -(w_0 * r_2))    v_2 = lin_2 + fma(w_0, r_1, -(w_1 * r_0))
+// xm.w (m_V), vf.w (flags), aux and the cold stores are not written.
+__global__ __launch_bounds__(TPB) void k_kinematic_apply(DevView d, KinPoses P) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= d.N) return;
+    float4 vf = d.vf[i];
+    const int fl = __float_as_int(vf.w);
+    if (!sph_is_static_rigid(fl)) return;
+    const int obj = sph_flags_object(fl);
+    int s = -1;
+    for (int k = 0; k < P.n; ++k) s = P.id[k] == obj ? k : s;
+    if (s < 0) return;
+    const int pid = __float_as_int(d.aux[i].w);
+    float4 xm = d.xm[i];
+    float q[3], r[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = __fsub_rn(d.x0_cold[3 * (size_t)pid + a], P.pivot[s][a]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        r[a] = __fmaf_rn(P.R[s][3 * a + 2], q[2], __fmaf_rn(P.R[s][3 * a + 1], q[1], __fmul_rn(P.R[s][3 * a], q[0])));
+    xm.x = __fadd_rn(P.origin[s][0], r[0]);
+    xm.y = __fadd_rn(P.origin[s][1], r[1]);
+    xm.z = __fadd_rn(P.origin[s][2], r[2]);
+    const float* w = P.ang[s];
+    vf.x = __fadd_rn(P.lin[s][0], __fmaf_rn(w[1], r[2], -__fmul_rn(w[2], r[1])));
+    vf.y = __fadd_rn(P.lin[s][1], __fmaf_rn(w[2], r[0], -__fmul_rn(w[0], r[2])));
+    vf.z = __fadd_rn(P.lin[s][2], __fmaf_rn(w[0], r[1], -__fmul_rn(w[1], r[0])));
+    d.xm[i] = xm;
+    d.vf[i] = vf;
+}
+
+// (x_0, flags) of every particle in the current order: what the host needs to know about the objects (sph_api.hip: obj_info)
+__global__ __launch_bounds__(TPB) void k_rest_records(DevView d, float4* __restrict__ out) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= d.N) return;
+    const int pid = __float_as_int(d.aux[i].w);
+    out[i] = make_float4(d.x0_cold[3 * (size_t)pid], d.x0_cold[3 * (size_t)pid + 1], d.x0_cold[3 * (size_t)pid + 2], d.vf[i].w);
+}
+
 // ---- field insert / extract (sph_upload / sph_download) -------------------
 __global__ __launch_bounds__(TPB) void k_extract(DevView d, int field, const int* __restrict__ color_cold,
                                                  void* __restrict__ out) {
@@ -1075,6 +1128,24 @@ int sphk_insert(SphContext* c, int field, const void* src) {
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_insert, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, field, c->x0_cold,
                        c->color_cold, src);
+    SPH_LAUNCH_CHECK(c);
+    return 0;
+}
+
+int sphk_rest_records(SphContext* c, float4* dst) {
+    if (c->N <= 0) return 0;
+    DevView d = sph_view(c);
+    hipLaunchKernelGGL(k_rest_records, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, dst);
+    SPH_LAUNCH_CHECK(c);
+    return 0;
+}
+
+// positions change outside the sweeps: the same event the advect and the rigid solve report
+int sphk_kinematic_apply(SphContext* c, const KinPoses& poses) {
+    sph_invalidate_lists(c);
+    if (c->N <= 0 || poses.n <= 0) return 0;
+    DevView d = sph_view(c);
+    hipLaunchKernelGGL(k_kinematic_apply, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, poses);
     SPH_LAUNCH_CHECK(c);
     return 0;
 }

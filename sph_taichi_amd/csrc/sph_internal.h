@@ -193,6 +193,12 @@ struct SphContext {
     bool slab_ev_open;  // slab mode: events [0..2] of ev[ev_used] are recorded, [3..4] follow in sph_slab_forces
     SphTimings tm;
     SphRender* render;
+    // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
+    double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
+    int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
+    SphKinematicMotion kin[SPH_MAX_KINEMATIC];
+    struct ObjInfo { int n, n_static; double lo[3], hi[3]; }* obj_info;  // [n_objects] particle counts (all / static solid) and rest AABB (x_0)
+    bool obj_info_valid;    // obj_info describes the current x_0 / object ids / flags (one download: sph_obj_info)
     char err[512];
 };
 
@@ -202,6 +208,11 @@ static inline hipStream_t sph_stream(const SphContext* c) { return c->use_side ?
 // particle positions / order / flags changed: neighbour lists and the non-empty-brick list are stale
 static inline void sph_invalidate_lists(SphContext* c) { sphd_invalidate(c->dv); }
 int sph_fail(SphContext* c, int code, const char* what);
+// a context that holds a window of the domain (a slab rank): what the frame export and the kinematic bodies refuse
+static inline bool sph_is_slab(const SphContext* c) {
+    return c->p.cell_origin[0] != 0 || c->p.cell_origin[1] != 0 || c->p.cell_origin[2] != 0 || c->p.cold_capacity > 0 ||
+           c->p.grid_num[0] != c->nx_alloc || c->opt_drop_outside || c->in_off != 0;
+}
 // the particle SET changed (records appended / dropped / re-selected): whatever a device-side check established about it is void
 static inline void sph_forget_pure_fluid(SphContext* c) { c->pure_fluid = 0; c->pure_fluid_n = -1; }
 // after a host synchronisation: did a device-side error flag rise since the last look (k_scan_fused's bounded wait)?  Marks the
@@ -252,6 +263,10 @@ int sphk_rigid_com(SphContext* c, int object_id, bool to_rest);
 int sphk_rigid_solve(SphContext* c, int object_id);
 int sphk_rigid_solve_all(SphContext* c, const int* ids, int n_ids, bool advect_first);  // every dynamic body + the solid wall passes, batched
 int sphk_extract(SphContext* c, int field, void* dst);
+// kinematic bodies: (x_0, flags) of every particle as float4 into `dst` (the staging buffer), and the pose kernel
+struct KinPoses { int n; int id[SPH_MAX_KINEMATIC]; float R[SPH_MAX_KINEMATIC][9], pivot[SPH_MAX_KINEMATIC][3], origin[SPH_MAX_KINEMATIC][3], lin[SPH_MAX_KINEMATIC][3], ang[SPH_MAX_KINEMATIC][3]; };
+int sphk_rest_records(SphContext* c, float4* dst);
+int sphk_kinematic_apply(SphContext* c, const KinPoses& poses);
 int sphk_insert(SphContext* c, int field, const void* src);
 void sph_render_release(SphContext* c);  // sph_render.hip: frees the frame-export buffers (sph_destroy)
 

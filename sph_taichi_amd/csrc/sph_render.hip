@@ -332,10 +332,7 @@ void sph_render_release(SphContext* c) {
 }
 
 // compositing across GPUs is not built: a context that holds a window of the domain refuses
-static bool render_is_slab(const SphContext* c) {
-    return c->p.cell_origin[0] != 0 || c->p.cell_origin[1] != 0 || c->p.cell_origin[2] != 0 || c->p.cold_capacity > 0 ||
-           c->p.grid_num[0] != c->nx_alloc || c->opt_drop_outside || c->in_off != 0;
-}
+static bool render_is_slab(const SphContext* c) { return sph_is_slab(c); }
 
 static SphRender* render_state(SphContext* c) {
     if (!c->render) {

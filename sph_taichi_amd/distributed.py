@@ -459,6 +459,9 @@ class SlabSolver:
         `recut_every` = K > 0: every K steps the ranks add up their per-layer particle counts and every cut plane
         moves ONE cell layer towards the position that balances the particle counts (`plan_recut`); the slab may
         grow by `nx_slack` layers over its initial width before the allocation is the limit."""
+        moved = [b.get("objectId") for key in ("RigidBlocks", "RigidBodies") for b in scene_dict.get(key, []) if b.get("motion") is not None]
+        if moved:     # (up front: before a device, a stream or a peer is touched)
+            raise NotImplementedError(f"kinematic bodies (\"motion\" of object(s) {moved}) exist on single-domain contexts only, not on slab ranks")
         import torch
         self.torch = torch
         self.rank, self.world = rank, world

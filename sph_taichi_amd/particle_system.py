@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, scene as _scene
+from . import _lib, motion as _motion, scene as _scene
 from .config_builder import SimConfig
 from .field import DeviceField, HostScalar
 
@@ -111,6 +111,9 @@ class ParticleSystem:
         if self.num_rigid_bodies > 0:
             self.rigid_rest_cm = DeviceField(self, F.F_RIGID_REST_CM, np.float32, lambda: sc.n_objects, 3, True,
                                              "rigid_rest_cm")
+        self._motions = dict(getattr(sc, "motions", {}))     # object id -> motion.Motion; pushed by SPHBase.initialize()
+        if self._motions and slab is not None:
+            raise NotImplementedError("kinematic bodies (\"motion\" in the scene file) exist on single-domain contexts only")
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -310,6 +313,98 @@ class ParticleSystem:
         mask = (self.object_id.to_numpy() == obj_id).nonzero()
         return {"position": self.x.to_numpy()[mask], "velocity": self.v.to_numpy()[mask]}
 
+    # ---- kinematic bodies (motion.py, include/sph_hip.h; the reference has none) ------
+    @property
+    def time(self) -> float:
+        """Simulated time (f64, held by the context): advanced by dt at the end of every step."""
+        t = C.c_double()
+        self._call("sph_get_time", C.byref(t))
+        return float(t.value)
+
+    @time.setter
+    def time(self, value: float):
+        self._call("sph_set_time", C.c_double(float(value)))
+
+    def _rest_positions(self, object_id):
+        return self.x_0.to_numpy()[self.object_id.to_numpy() == int(object_id)]
+
+    def _push_motions(self):
+        """Hand the registered motions to the library (all at once: it replaces the set).  On failure the library keeps
+        the set it had."""
+        arr = (_lib.SphKinematicMotion * max(len(self._motions), 1))()
+        for k, (oid, m) in enumerate(sorted(self._motions.items())):
+            arr[k] = _motion.to_struct(oid, m)
+        self._call("sph_kinematic_set", arr, len(self._motions))
+
+    def set_body_motion(self, object_id: int, **motion):
+        """Prescribe the motion of a non-dynamic solid object from the next step on: the keys of a scene file's
+        "motion" entry (linearVelocity, angularVelocity, pivot, oscillation, startTime, endTime; see motion.py).
+        Times are on the clock `ps.time`.  Replaces the object's earlier motion."""
+        oid = int(object_id)
+        obj = self.object_collection.get(oid, {})
+        m = _motion.parse_motion(motion, is_dynamic=bool(obj.get("isDynamic")))
+        if m.pivot is None:
+            rest = self._rest_positions(oid)
+            if rest.shape[0] == 0:
+                raise ValueError(f"set_body_motion: object {oid} has no particles")
+            m.with_pivot(rest)
+        if oid not in self._motions and len(self._motions) >= _motion.MAX_KINEMATIC:
+            raise ValueError(f"set_body_motion: at most {_motion.MAX_KINEMATIC} objects can be kinematic")
+        old = self._motions.get(oid)
+        self._motions[oid] = m
+        try:
+            self._push_motions()
+        except _lib.SphError:
+            if old is None:
+                del self._motions[oid]
+            else:
+                self._motions[oid] = old
+            raise
+
+    def clear_body_motion(self, object_id: int):
+        """The object is no longer moved: it stays at the pose of the current time, at rest (a static solid again)."""
+        m = self._motions.get(int(object_id))
+        if m is None:
+            return
+        R, c, _, _ = _motion.pose(m, self.time)
+        self.set_body_pose(object_id, R, c, pivot=m.pivot)
+        del self._motions[int(object_id)]
+        self._push_motions()
+
+    def set_body_pose(self, object_id: int, R, origin, lin_vel=(0.0, 0.0, 0.0), ang_vel=(0.0, 0.0, 0.0), pivot=None):
+        """Place a non-dynamic solid object now: x = origin + R (x_0 - pivot), v = lin_vel + ang_vel x (x - origin), for
+        trajectories scripted from Python.  `pivot` defaults to the mean of the object's rest positions.  Enqueues."""
+        p = _lib.SphBodyPose()
+        p.object_id = int(object_id)
+        if pivot is None:
+            rest = self._rest_positions(object_id)
+            if rest.shape[0] == 0:
+                raise ValueError(f"set_body_pose: object {int(object_id)} has no particles")
+            pivot = rest.astype(np.float64).mean(axis=0)
+        p.R = (C.c_float * 9)(*[float(v) for v in np.asarray(R, dtype=np.float64).reshape(9)])
+        for name, val in (("pivot", pivot), ("origin", origin), ("lin_vel", lin_vel), ("ang_vel", ang_vel)):
+            setattr(p, name, (C.c_float * 3)(*[float(v) for v in np.asarray(val, dtype=np.float64).reshape(3)]))
+        self._call("sph_kinematic_apply", C.byref(p), 1)
+
+    def _kinematic_reference_step(self, dt: float):
+        """What the device loop does at the end of a step, for the step made of individual calls (SPHBase._reference_step):
+        the clock advances by the f32 dt the library holds, registered objects go to the pose of the new time."""
+        t = self.time + float(np.float32(dt))
+        for oid, m in sorted(self._motions.items()):
+            R, c, u, w = _motion.pose(m, t)
+            self.set_body_pose(oid, R, c, u, w, pivot=m.pivot)
+        self.time = t
+
+    def update_kinematic_meshes(self):
+        """OBJ export: the export mesh of every kinematic RigidBody at the body's current pose -- R and origin applied to
+        `restPosition` on the host, like the dynamic bodies' mesh update (SPHBase.solve_rigid_body)."""
+        t = self.time
+        for oid, m in self._motions.items():
+            obj = self.object_collection.get(oid)
+            if obj is not None and "mesh" in obj:
+                R, c, _, _ = _motion.pose(m, t)
+                obj["mesh"].vertices = c + (np.asarray(obj["restPosition"], dtype=np.float64) - m.pivot) @ R.T
+
     # ---- state checkpoint (SURVEY 8 f3; the reference has none) ----------------------
     _STATE_FIELDS = ("object_id", "x", "x_0", "v", "acceleration", "m_V", "m", "density", "pressure", "material",
                      "color", "is_dynamic", "pid")
@@ -331,6 +426,7 @@ class ParticleSystem:
         if self.num_rigid_bodies > 0:
             data["rigid_rest_cm"] = self.rigid_rest_cm.to_numpy()
         data["particle_max_num"] = np.int64(self.particle_max_num)
+        data["sim_time"] = np.float64(self.time)       # the clock: a restarted run continues a prescribed motion exactly
         for k, v in meta.items():
             data["meta_" + k] = np.asarray(v)
         np.savez_compressed(path, **data)
@@ -345,6 +441,8 @@ class ParticleSystem:
                 getattr(self, f).from_numpy(z[f])
         if "rigid_rest_cm" in z.files and self.num_rigid_bodies > 0:
             self.rigid_rest_cm.from_numpy(z["rigid_rest_cm"])
+        if "sim_time" in z.files:
+            self.time = float(z["sim_time"])
         return {k[5:]: z[k] for k in z.files if k.startswith("meta_")}
 
     # ---- frame export (run_simulation.py:37-98 of the reference: the window; here an image made on the device) ----

@@ -102,6 +102,7 @@ def main(argv=None):
                 np_pos = ps.dump(obj_id=obj_id)["position"]
                 write_ply_ascii(series_prefix.format(0).replace(".ply", f"_{cnt_ply:06}.ply"), np_pos)
             if output_obj:
+                ps.update_kinematic_meshes()       # kinematic bodies ("motion"): the mesh at the current pose
                 for r_body_id in ps.object_id_rigid_body:
                     with open(f"{scene_name}_output/obj_{r_body_id}_{cnt_ply:06}.obj", "w") as f:
                         f.write(ps.object_collection[r_body_id]["mesh"].export(file_type="obj"))

@@ -11,7 +11,7 @@ from functools import reduce
 
 import numpy as np
 
-from . import voxelizer
+from . import motion as _motion, voxelizer
 
 MATERIAL_SOLID = 0   # particle_system.py:30
 MATERIAL_FLUID = 1   # particle_system.py:31
@@ -248,6 +248,18 @@ def build_scene(cfg, base_dir: str | None = None, verbose: bool = False, x_filte
                          f"{sc.particle_max_num} (the reference would overflow its fields here)")
     sc.arrays = b.arrays()
     sc.dynamic_rigid_ids = [oid for oid in sc.object_id_rigid_body if sc.object_collection[oid]["isDynamic"]]
+    # ---- kinematic bodies: "motion" of a non-dynamic RigidBlock / RigidBody (motion.py; no reference counterpart) ----
+    sc.motions = {}
+    for obj in list(rigid_blocks) + list(rigid_bodies):
+        if obj.get("motion") is not None:
+            oid = obj["objectId"]
+            rest = sc.arrays["x_0"][sc.arrays["object_id"] == oid]
+            if rest.shape[0] == 0 and obj["motion"].get("pivot") is None:
+                raise ValueError(f"motion of object {oid}: no rest positions here to take the default pivot from; give a pivot")
+            sc.motions[oid] = _motion.parse_motion(obj["motion"], is_dynamic=bool(obj.get("isDynamic")),
+                                                   rest_positions=rest if rest.shape[0] else None)
+    if len(sc.motions) > _motion.MAX_KINEMATIC:
+        raise ValueError(f"{len(sc.motions)} objects have a motion; at most {_motion.MAX_KINEMATIC} can be kinematic")
     return sc
 
 

@@ -50,6 +50,8 @@ class SPHBase:
                 self.ps.set_option(_lib.OPT_RIGID_SUMS_FROM_X0, 0)
         self.compute_static_boundary_volume()
         self.compute_moving_boundary_volume()
+        if getattr(self.ps, "_motions", None):
+            self.ps._push_motions()         # kinematic bodies of the scene file ("motion"): moved from the first step on
 
     def compute_rigid_rest_cm(self, object_id: int):
         self.ps._call("sph_compute_rigid_rest_cm", int(object_id))
@@ -108,6 +110,7 @@ class SPHBase:
             self.enforce_boundary_2D(self.ps.material_fluid)
         elif self.ps.dim == 3:
             self.enforce_boundary_3D(self.ps.material_fluid)
+        self.ps._kinematic_reference_step(self.dt[None])    # the clock, and kinematic bodies to the pose of the step's end
 
     def step(self):
         self._reference_step()
