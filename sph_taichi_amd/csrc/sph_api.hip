@@ -56,12 +56,10 @@ DevView sph_view(const SphContext* c) {
     d.stg = c->stg; d.gat = c->gat; d.kbuf = reinterpret_cast<float*>(c->gat);
     d.m_u = c->m_uniform; d.write_sg = 0; d.write_k = 0;
     d.whx = p.wall_hi[0]; d.why = p.wall_hi[1]; d.whz = p.wall_hi[2];
-    d.fuse_advect = c->fuse_advect;
-    d.df_bpart = c->df_collect ? c->df_bpart : nullptr;
+    d.fuse_advect = 0; d.store_acc = 1; d.df_bpart = nullptr;   // per launch: launch_brick_cfg fills them from its SweepArgs
     d.gate = (c->df_epoch && c->opt_df_runahead) ? c->df_gate : nullptr;   // (without run-ahead no body is ever enqueued past convergence)
     d.gate_epoch = c->df_epoch;
     d.fx_scale = ldexp(1.0, c->rigid_fx_exp);
-    d.store_acc = !(c->fuse_advect && c->skip_acc);
     d.rigid_from_x0 = 0;   // set by the two launchers the option speaks of (sphk_rigid_com to_rest, sphk_rigid_partial16)
     return d;
 }
@@ -306,7 +304,6 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     c->opt_brick_shape = 0;
     c->opt_rigid_batch = 1;
     c->opt_df_fuse_err = 1;
-    c->df_collect = 0;
     c->opt_df_runahead = 0;   // measured (r05): running ahead costs 2 % more than the bubbles it removes
     c->opt_exact_math = 0;
     c->opt_rigid_x0 = 0;
@@ -634,11 +631,11 @@ int32_t sph_prefix_sum(SphContext* c) {
     return 0;
 }
 
-static int counting_sort(SphContext* c, bool sort_acc) {
+static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets = nullptr) {
     if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_counting_sort before sph_prefix_sum");
     int rc = refresh_dyn(c);
     if (rc) return rc;
-    rc = sphk_sort_scatter(c, sort_acc);
+    rc = sphk_sort_scatter(c, sort_acc, deliver_offsets);
     if (rc) return rc;
     c->in_off = 0;         // the scatter writes the other set from record 0
     c->have_keys = false;  // the histogram offsets are consumed
@@ -771,6 +768,16 @@ static int harvest_events(SphContext* c) {
     return 0;
 }
 
+// the timed-step prologue: *ev = the five events of the step that starts now, ev[0] recorded -- or null (not a timed step)
+static int timed_step_begin(SphContext* c, hipEvent_t** ev) {
+    *ev = nullptr;
+    if (!sph_timed_step(c)) return 0;
+    if (c->ev_used == SPH_MAX_TIMED_STEPS) { int rc = harvest_events(c); if (rc) return rc; }
+    *ev = c->ev[c->ev_used];
+    SPH_HIP(c, hipEventRecord((*ev)[0], c->stream));
+    return 0;
+}
+
 // uniform-fluid force path: decide (once per change of the particle set) whether its precondition holds
 static int uniform_fluid(SphContext* c) {
     // (a slab rank with dynamic solids computes forces on its first ghost layer too, whose neighbours in the outer
@@ -783,15 +790,23 @@ static int uniform_fluid(SphContext* c) {
     return sphk_check_uniform_fluid(c);
 }
 
-// sweeps of one step after the sort; ev (nullable) = the step's 5 events, ev[1] already recorded
-static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic) {
+// compute_moving_boundary_volume() (sph_base.py:265), the uniform-fluid decision, density + EOS (WCSPH.py:153, :74-76).
+// The boundary volume goes first, the reference's order.  (The slab entry points used to decide first: the same thing.  The
+// decision's check kernel -- launched only when the particle set changed -- reads mass and m_V of FLUID particles and writes
+// the staging buffer; the boundary-volume sweep writes m_V of dynamic SOLID particles and reads no staging.)
+static int density_phase(SphContext* c) {
+    int rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;
+    rc = rc ? rc : uniform_fluid(c);
+    return rc ? rc : sphk_gather(c, GM_DENSITY_EOS);
+}
+
+// sweeps of one step after the sort; ev (nullable) = the step's 5 events, ev[1] already recorded.  last_step: false for a
+// step of sph_step(n) that is not the call's last -- only the last one's acceleration can ever be read.
+static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic, bool last_step) {
     int rc = 0;
     bool fused_advect = false;
-    // compute_moving_boundary_volume()                     sph_base.py:265
-    if (c->n_dyn_host > 0) { rc = sphk_gather(c, GM_BVOL_DYNAMIC); if (rc) return rc; }
     if (c->opt_fused) {
-        rc = uniform_fluid(c);
-        rc = rc ? rc : sphk_gather(c, GM_DENSITY_EOS);      // WCSPH.py:153 (+ EOS of :74-76)
+        rc = density_phase(c);
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
         // With the one-gather force sweep no workgroup reads another particle's xm / vf (neighbours come from the
@@ -800,13 +815,15 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
         // they are integrated afterwards, by a kernel over their (short) list.
         const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && !c->opt_drop_outside &&
                           c->opt_gather_impl == 1 && c->N > 0;
-        c->fuse_advect = fuse ? 1 : 0;
-        rc = sphk_gather(c, GM_FORCE_FUSED);                // WCSPH.py:154-155 (+ :156 and sph_base.py:270-271 when fused)
-        c->fuse_advect = 0;
+        SweepArgs force;
+        force.fuse_advect = fuse;
+        force.store_acc = last_step;
+        rc = sphk_gather(c, GM_FORCE_FUSED, force);         // WCSPH.py:154-155 (+ :156 and sph_base.py:270-271 when fused)
         if (rc) return rc;
         fused_advect = fuse;
     } else {
-        rc = sphk_gather(c, GM_DENSITY);
+        rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
+        rc = rc ? rc : sphk_gather(c, GM_DENSITY);
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
         rc = sphk_gather(c, GM_NONPRESSURE);
@@ -822,6 +839,14 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
     if (rc) return rc;
     if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }
     return 0;
+}
+
+// hash + scan + scatter without touching aux: for callers that run a density sweep right behind it (nothing can read the
+// stale density / pressure copies the scatter moves in between; the acceleration is dead there too)
+static int sort_no_fold(SphContext* c, const CellIdx16* deliver_offsets = nullptr) {
+    int rc = sph_update_grid_id(c);
+    rc = rc ? rc : sph_prefix_sum(c);
+    return rc ? rc : counting_sort(c, false, deliver_offsets);
 }
 
 int32_t sph_set_target_layers(SphContext* c, int32_t dlo, int32_t dhi, int32_t flo, int32_t fhi) {
@@ -850,14 +875,6 @@ int32_t sph_slab_set_window(SphContext* c, int32_t origin_x, int32_t nx) {
     return 0;
 }
 
-// hash + scan + scatter without touching aux: for callers that run a density sweep right behind it (nothing can read the
-// stale density / pressure copies the scatter moves in between)
-static int sort_no_fold(SphContext* c) {
-    int rc = sph_update_grid_id(c);
-    rc = rc ? rc : sph_prefix_sum(c);
-    return rc ? rc : counting_sort(c, false);
-}
-
 int32_t sph_sort(SphContext* c) {
     ENTER(c);
     // (after the lean density finish, density / pressure live in eos2 in the OLD order; a stand-alone sort must
@@ -872,12 +889,18 @@ int32_t sph_sweeps(SphContext* c) {
     int rc = need_sorted(c, "sph_sweeps");
     rc = rc ? rc : refresh_dyn(c);
     if (rc) return rc;
-    return step_sweeps(c, nullptr, nullptr, 0);
+    return step_sweeps(c, nullptr, nullptr, 0, true);
 }
 
-int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
-    ENTER(c);
-    if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) return sph_fail(c, SPH_E_INVALID, "sph_step: bad arguments");
+// The frame of both step loops = SPHBase.step() (sph_base.py:263-271) n_steps times.  `body` is the solver's part of one step, between
+// the sort (ev[1] recorded) and the kinematic poses: it records ev[2] and ev[3] of a timed step.
+typedef int (*StepBody)(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic, bool last_step);
+
+static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
+    if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) {
+        snprintf(c->err, sizeof(c->err), "%s: bad arguments", who);
+        return SPH_E_INVALID;
+    }
     int rc = refresh_dyn(c);
     if (rc) return rc;
     int kin_rc = 0;
@@ -888,22 +911,12 @@ int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int
     if (n_steps > 0) c->acc_partial = false;   // the call's last step writes every acceleration out
     for (int it = 0; it < n_steps; ++it) {
         const double t_end = c->sim_time + (double)c->p.dt;
-        hipEvent_t* ev = nullptr;
-        const bool timing = sph_timed_step(c);  // SPH_OPT_TIMING k: every k-th step carries the five events
-        if (timing) {
-            if (c->ev_used == SPH_MAX_TIMED_STEPS) { rc = harvest_events(c); if (rc) return rc; }
-            ev = c->ev[c->ev_used];
-            SPH_HIP(c, hipEventRecord(ev[0], c->stream));
-        }
-        // ps.initialize_particle_system()                      sph_base.py:264
-        rc = sph_update_grid_id(c);
-        rc = rc ? rc : sph_prefix_sum(c);
-        rc = rc ? rc : counting_sort(c, false);  // acceleration is dead here: every particle's a is rewritten below
+        hipEvent_t* ev = nullptr;   // SPH_OPT_TIMING k: every k-th step carries the five events
+        rc = timed_step_begin(c, &ev);
+        rc = rc ? rc : sort_no_fold(c);   // ps.initialize_particle_system()   sph_base.py:264
         if (rc) return rc;
-        if (timing) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
-        c->skip_acc = it + 1 < n_steps;  // only the acceleration of the call's last step can ever be read
-        rc = step_sweeps(c, ev, dynamic_ids, n_dynamic);
-        c->skip_acc = 0;
+        if (ev) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
+        rc = body(c, ev, dynamic_ids, n_dynamic, it + 1 == n_steps);
         if (rc) return rc;
         if (c->n_kin > 0) {   // registered bodies -> pose(t_end)
             KinPoses kin;
@@ -912,9 +925,14 @@ int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int
             if (rc) return rc;
         }
         c->sim_time = t_end;
-        if (timing) { SPH_HIP(c, hipEventRecord(ev[4], c->stream)); c->ev_used++; }
+        if (ev) { SPH_HIP(c, hipEventRecord(ev[4], c->stream)); c->ev_used++; }
     }
     return kin_rc;
+}
+
+int32_t sph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
+    ENTER(c);
+    return step_loop(c, "sph_step", step_sweeps, n_steps, dynamic_ids, n_dynamic);
 }
 
 // ---- multi-GPU slab support ---------------------------------------------------
@@ -1110,11 +1128,7 @@ int32_t sph_slab_advance(SphContext* c, int32_t keep_first, int32_t keep_count, 
     // following sph_slab_forces (force, advect); the halo exchange itself is host-side and not on this stream
     hipEvent_t* ev = nullptr;
     c->slab_ev_open = false;
-    if (do_sweeps == 2 && sph_timed_step(c)) {
-        if (c->ev_used == SPH_MAX_TIMED_STEPS) { int rh = harvest_events(c); if (rh) return rh; }
-        ev = c->ev[c->ev_used];
-        SPH_HIP(c, hipEventRecord(ev[0], c->stream));
-    }
+    if (do_sweeps == 2) { int rt = timed_step_begin(c, &ev); if (rt) return rt; }
     // do_sweeps != 0: a density sweep follows at once and rewrites every fluid particle's density / pressure -- the stale
     // copies the scatter moves are never observable (the received records' neither: their owner's sweep is as old as
     // ours).  do_sweeps == 0: the caller may read the fields next, so they are folded into aux first -- before
@@ -1128,10 +1142,10 @@ int32_t sph_slab_advance(SphContext* c, int32_t keep_first, int32_t keep_count, 
     // launch of its own between the scatter and the density sweep and an event record behind it, ~8 us on the stream of every
     // slab step; the host now also gets the offsets a scatter earlier)
     if (!rc && (!layers || n_layers < 0 || n_layers > 16)) rc = SPH_E_INVALID;
-    if (!rc) rc = layer_offset_cells(c, layers, n_layers, &c->off_ix);
-    if (!rc) { c->off_in_sort = true; c->off_stamp_pending = false; }
-    rc = rc ? rc : sort_no_fold(c);
-    c->off_in_sort = false;
+    CellIdx16 offset_cells;
+    if (!rc) rc = layer_offset_cells(c, layers, n_layers, &offset_cells);
+    if (!rc) c->off_stamp_pending = false;
+    rc = rc ? rc : sort_no_fold(c, &offset_cells);
     // an EMPTY record set launches no place kernel, so nobody writes the offsets or the stamp: every count below every layer is 0
     // (sph_layer_offsets_end then neither spins nor reads the mapped words of an earlier step)
     if (!rc && !c->off_stamp_pending) c->off_zero_mask = 0xffff;
@@ -1139,9 +1153,7 @@ int32_t sph_slab_advance(SphContext* c, int32_t keep_first, int32_t keep_count, 
     if (!rc && do_sweeps == 1) rc = sph_sweeps(c);
     if (!rc && do_sweeps == 2) {  // boundary volume + density only; sph_slab_forces does the rest
         rc = refresh_dyn(c);
-        rc = rc ? rc : uniform_fluid(c);
-        if (!rc && c->n_dyn_host > 0) rc = sphk_gather(c, GM_BVOL_DYNAMIC);
-        rc = rc ? rc : sphk_gather(c, GM_DENSITY_EOS);
+        rc = rc ? rc : density_phase(c);
         if (!rc && ev) { SPH_HIP(c, hipEventRecord(ev[2], c->stream)); c->slab_ev_open = true; }
     }
     return rc;
@@ -1173,29 +1185,31 @@ int32_t sph_slab_forces(SphContext* c, int32_t bl_lo, int32_t bl_hi, int32_t br_
     if (!no_side) {
         SPH_HIP(c, hipEventRecord(c->ev_fork, c->stream));
         SPH_HIP(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        c->use_side = true;
     }
-    rc = sphk_gather_layers(c, GM_FORCE_FUSED, f_lo, bl_hi, br_lo, f_hi);
+    SweepArgs boundary;
+    boundary.lo = f_lo; boundary.hi = bl_hi; boundary.lo2 = br_lo; boundary.hi2 = f_hi;
+    boundary.side = !no_side;
+    const hipStream_t bst = no_side ? c->stream : c->side;
+    rc = sphk_gather_layers(c, GM_FORCE_FUSED, boundary);
     // the packed layers' dynamic solids: their coupling reactions all come from the boundary sets (which reach one
     // layer further in for that), so they are complete now and the packers can advance them
-    rc = rc ? rc : sphk_fold_coupling_range(c, firstL, nL);
-    rc = rc ? rc : sphk_fold_coupling_range(c, firstR, nR);
-    rc = rc ? rc : sphk_pack_advected(c, firstL, nL, dstL);
-    rc = rc ? rc : sphk_pack_advected(c, firstR, nR, dstR);
-    c->use_side = false;
+    rc = rc ? rc : sphk_fold_coupling_range(c, firstL, nL, bst);
+    rc = rc ? rc : sphk_fold_coupling_range(c, firstR, nR, bst);
+    rc = rc ? rc : sphk_pack_advected(c, firstL, nL, dstL, bst);
+    rc = rc ? rc : sphk_pack_advected(c, firstR, nR, dstR, bst);
     if (rc) return rc;
-    if (!no_boundary) SPH_HIP(c, hipEventRecord(c->ev_pack, no_side ? c->stream : c->side));
+    if (!no_boundary) SPH_HIP(c, hipEventRecord(c->ev_pack, bst));
     // interior: overlaps with the exchange; with the one-gather sweep its finish integrates its own targets (see
     // step_sweeps), so that afterwards only the two boundary ranges -- exactly the packed ranges -- are left to advect
     // (ghost records are not advected at all: the exchange replaces them)
     const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && c->opt_no_dynamic;
-    c->fuse_advect = fuse ? 1 : 0;
     // (an interior target's acceleration is consumed by the advect in the same finish and by nobody else -- the packers
     // read the BOUNDARY sets' -- so, as inside sph_step, it is not written out: 16 B per particle and step less)
-    c->skip_acc = fuse ? 1 : 0;
-    rc = sphk_gather_layers(c, GM_FORCE_FUSED, bl_hi, br_lo, 0, 0);
-    c->fuse_advect = 0;
-    c->skip_acc = 0;
+    SweepArgs interior;
+    interior.lo = bl_hi; interior.hi = br_lo;
+    interior.fuse_advect = fuse;
+    interior.store_acc = !fuse;
+    rc = sphk_gather_layers(c, GM_FORCE_FUSED, interior);
     c->acc_partial = fuse;
     if (rc) return rc;
     if (!no_boundary) SPH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_pack, 0));  // the packers read what the advect overwrites
@@ -1223,9 +1237,7 @@ int32_t sph_slab_density(SphContext* c) {
     ENTER(c);
     int rc = need_sorted(c, "sph_slab_density");
     rc = rc ? rc : refresh_dyn(c);
-    rc = rc ? rc : uniform_fluid(c);
-    if (!rc && c->n_dyn_host > 0) rc = sphk_gather(c, GM_BVOL_DYNAMIC);
-    return rc ? rc : sphk_gather(c, GM_DENSITY_EOS);
+    return rc ? rc : density_phase(c);
 }
 
 int32_t sph_rigid_partial_sums(SphContext* c, int32_t object_id, int32_t first, int32_t count, double* dev_sums16) {
@@ -1348,10 +1360,10 @@ struct DfSolve { int sweep, refresh; float offset; double eta; int limit; };
 static int df_enqueue_body(SphContext* c, const DfSolve& s, int k) {
     int rc = sphk_gather(c, s.sweep);                    // *_solver_iteration(): kernel,
     // (the refresh sweep also reduces the density error over its own targets, brick by brick, when it runs as a brick sweep)
-    c->df_collect = c->opt_df_fuse_err;
+    SweepArgs refresh;
+    refresh.collect_bpart = c->opt_df_fuse_err != 0;
     sphd_bpart_consumed(c->dv);
-    rc = rc ? rc : sphk_gather(c, s.refresh);            //   compute_density_change() / compute_density_adv(),
-    c->df_collect = 0;
+    rc = rc ? rc : sphk_gather(c, s.refresh, refresh);   //   compute_density_change() / compute_density_adv(),
     rc = rc ? rc : sphk_df_convergence_test(c, s.offset, s.eta, k & 3);  // compute_density_error() + the test
     if (rc) return rc;
     SPH_HIP(c, hipEventRecord(c->ev_df[k & 3], c->stream));
@@ -1439,57 +1451,30 @@ int32_t sph_dfsph_pressure_solve(SphContext* c) {
     return 0;
 }
 
+// one step of DFSPHSolver between the sort and the kinematic poses (step_loop)
+static int dfsph_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic, bool) {
+    int rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
+    // DFSPHSolver.substep (DFSPH.py:400-408)
+    rc = rc ? rc : sphk_gather(c, GM_DF_DENSITY);
+    rc = rc ? rc : sphk_gather(c, GM_DF_FACTOR);
+    if (rc) return rc;
+    if (ev) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
+    if (c->df.enable_divergence_solver) { rc = sph_dfsph_divergence_solve(c); if (rc) return rc; }
+    rc = sphk_gather(c, GM_DF_NONPRESSURE);
+    rc = rc ? rc : sphk_df_predict_velocity(c);
+    rc = rc ? rc : sph_dfsph_pressure_solve(c);
+    if (rc) return rc;
+    if (ev) SPH_HIP(c, hipEventRecord(ev[3], c->stream));
+    rc = sphk_df_advect(c, true);                                // advect + enforce_boundary_3D(fluid)
+    if (rc) return rc;
+    if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }  // solve_rigid_body()  sph_base.py:247-260
+    c->df_stats.steps++;
+    return 0;
+}
+
 int32_t sph_dfsph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
     ENTER(c);
-    if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) return sph_fail(c, SPH_E_INVALID, "sph_dfsph_step: bad arguments");
-    int rc = refresh_dyn(c);
-    if (rc) return rc;
-    int kin_rc = 0;
-    if (c->n_kin > 0) {   // registered kinematic bodies: only the steps that keep them inside the domain are enqueued
-        kin_rc = kin_admit(c, n_steps, &n_steps);
-        if (kin_rc && kin_rc != SPH_E_INVALID) return kin_rc;
-    }
-    if (n_steps > 0) c->acc_partial = false;
-    for (int it = 0; it < n_steps; ++it) {
-        const double t_end = c->sim_time + (double)c->p.dt;
-        hipEvent_t* ev = nullptr;
-        const bool timing = sph_timed_step(c);  // SPH_OPT_TIMING k: every k-th step carries the five events
-        if (timing) {
-            if (c->ev_used == SPH_MAX_TIMED_STEPS) { rc = harvest_events(c); if (rc) return rc; }
-            ev = c->ev[c->ev_used];
-            SPH_HIP(c, hipEventRecord(ev[0], c->stream));
-        }
-        rc = sph_update_grid_id(c);                                  // sph_base.py:264
-        rc = rc ? rc : sph_prefix_sum(c);
-        rc = rc ? rc : counting_sort(c, false);
-        if (rc) return rc;
-        if (timing) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
-        if (c->n_dyn_host > 0) { rc = sphk_gather(c, GM_BVOL_DYNAMIC); if (rc) return rc; }  // sph_base.py:265
-        // DFSPHSolver.substep (DFSPH.py:400-408)
-        rc = sphk_gather(c, GM_DF_DENSITY);
-        rc = rc ? rc : sphk_gather(c, GM_DF_FACTOR);
-        if (rc) return rc;
-        if (timing) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
-        if (c->df.enable_divergence_solver) { rc = sph_dfsph_divergence_solve(c); if (rc) return rc; }
-        rc = sphk_gather(c, GM_DF_NONPRESSURE);
-        rc = rc ? rc : sphk_df_predict_velocity(c);
-        rc = rc ? rc : sph_dfsph_pressure_solve(c);
-        if (rc) return rc;
-        if (timing) SPH_HIP(c, hipEventRecord(ev[3], c->stream));
-        rc = sphk_df_advect(c, true);                                // advect + enforce_boundary_3D(fluid)
-        if (rc) return rc;
-        if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }  // solve_rigid_body()  sph_base.py:247-260
-        if (c->n_kin > 0) {   // registered bodies -> pose(t_end)
-            KinPoses kin;
-            kin_poses_at(c, t_end, &kin);
-            rc = sphk_kinematic_apply(c, kin);
-            if (rc) return rc;
-        }
-        c->sim_time = t_end;
-        if (timing) { SPH_HIP(c, hipEventRecord(ev[4], c->stream)); c->ev_used++; }
-        c->df_stats.steps++;
-    }
-    return kin_rc;
+    return step_loop(c, "sph_dfsph_step", dfsph_sweeps, n_steps, dynamic_ids, n_dynamic);
 }
 
 #ifdef SPH_PROFILE

@@ -1551,13 +1551,13 @@ int sphk_fold_coupling(SphContext* c) {
     return 0;
 }
 
-// the same for the records [first, first + count) only, on the stream the sweeps of the moment run on (slab mode:
+// the same for the records [first, first + count) only, on the stream of the sweep that scattered to them (slab mode:
 // the halo packers advance the boundary layers' records right behind the boundary force launch and need those
 // particles' reactions -- complete by then, sph_slab_forces -- while the interior launch is still scattering to others)
-int sphk_fold_coupling_range(SphContext* c, int first, int count) {
+int sphk_fold_coupling_range(SphContext* c, int first, int count, hipStream_t st) {
     if (c->opt_no_dynamic || c->n_dyn_host == 0 || count <= 0) return 0;
     DevView d = sph_view(c);
-    hipLaunchKernelGGL(k_fold_coupling, dim3((count + TPB - 1) / TPB), dim3(TPB), 0, sph_stream(c), d, (const int*)nullptr, first, count);
+    hipLaunchKernelGGL(k_fold_coupling, dim3((count + TPB - 1) / TPB), dim3(TPB), 0, st, d, (const int*)nullptr, first, count);
     SPH_LAUNCH_CHECK(c);
     return 0;
 }
@@ -1657,13 +1657,16 @@ int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a, SphPartKey* key) {
 }
 
 template <int MODE, class CFG, int VAR = 0>
-static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0, int hi2 = 0) {
+static int launch_brick_cfg(SphContext* c, const SweepArgs& a) {
     DevView d = sph_view(c);
+    d.fuse_advect = a.fuse_advect;
+    d.store_acc = a.store_acc || !a.fuse_advect;  // (only the fused advect has consumed the acceleration it does not store)
+    d.df_bpart = a.collect_bpart ? c->df_bpart : nullptr;
     if (MODE == GM_DENSITY_EOS) { d.tgt_lo = c->tgt_layers[0]; d.tgt_hi = c->tgt_layers[1]; d.write_sg = c->uniform_state == 1; }
     if (MODE == GM_DF_DENSITY) d.write_sg = 1;
     if (mode_is_df_vdiv<MODE>()) d.write_k = 1;
     if (MODE == GM_FORCE_FUSED || MODE == GM_FORCE_FUSED_U) { d.tgt_lo = c->tgt_layers[2]; d.tgt_hi = c->tgt_layers[3]; }
-    if (lo >= 0) { d.tgt_lo = lo; d.tgt_hi = hi; d.tgt_lo2 = lo2; d.tgt_hi2 = hi2; }
+    if (a.lo >= 0) { d.tgt_lo = a.lo; d.tgt_hi = a.hi; d.tgt_lo2 = a.lo2; d.tgt_hi2 = a.hi2; }
     if (d.tgt_hi2 <= d.tgt_lo2) d.tgt_lo2 = d.tgt_hi2 = 0;
     if (d.tgt_hi <= d.tgt_lo) { d.tgt_lo = d.tgt_lo2; d.tgt_hi = d.tgt_hi2; d.tgt_lo2 = d.tgt_hi2 = 0; }
     if (d.tgt_hi <= d.tgt_lo) return 0;
@@ -1687,9 +1690,9 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
     const int fixed_bz = c->opt_brick_shape == 1 ? CFG::BZ : 0;
     const int tmax = TPB, smax = brick_smax(c);
     const SphPartKey key = brick_key(c, d);
-    hipStream_t st = sph_stream(c);
-    int2* blist = c->use_side ? c->brick_list2 : c->brick_list;
-    int* bcount = c->use_side ? c->brick_count2 : c->brick_count;
+    hipStream_t st = a.side ? c->side : c->stream;
+    int2* blist = a.side ? c->brick_list2 : c->brick_list;
+    int* bcount = a.side ? c->brick_count2 : c->brick_count;
     // A cached list also serves a sweep whose target ranges lie INSIDE the cached (single) one -- slab mode: the force
     // sweeps over the boundary layers (side stream) and the interior after the density sweep over owned + first ghost
     // layers. Bricks listed for the wider range that hold no target of this sweep leave at T == 0. For a sweep that
@@ -1700,13 +1703,13 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
     } else {
         if (mode_reads_list<MODE>())
             return sph_fail(c, SPH_E_INVALID, "the sweep reads neighbour lists but its targets lie outside the partition that wrote them");
-        if (c->use_side || !sphd_count_is_zero(c->dv)) SPH_HIP(c, hipMemsetAsync(bcount, 0, 2 * sizeof(int), st));
+        if (a.side || !sphd_count_is_zero(c->dv)) SPH_HIP(c, hipMemsetAsync(bcount, 0, 2 * sizeof(int), st));
         hipLaunchKernelGGL((k_brick_list<CFG>), dim3((ncg + TPB / 64 - 1) / (TPB / 64)), dim3(TPB), (size_t)(TPB / 64) * 5 * (d.nz + 1) * sizeof(int),
                            st, d, nbx, nby, blist, bcount, c->brick_cap, tmax, smax, fixed_bz);
         SPH_LAUNCH_CHECK(c);
         // (the side stream's list is private to that launch and never cached)  The main stream's replaces the cached one, and
         // the lists and column records written over that one go with it: their entries are relative to ITS bricks.
-        if (!c->use_side) sphd_partition_rebuilt(c->dv, key);
+        if (!a.side) sphd_partition_rebuilt(c->dv, key);
     }
     // the per-brick column records: written by a list-writing sweep over the cached list of the main stream, read back by
     // the list readers whose target ranges are exactly the writer's (a subset sweep -- slab mode -- has other target tables)
@@ -1728,73 +1731,74 @@ static int launch_brick_cfg(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0
 }
 
 template <int MODE>
-static int launch_brick(SphContext* c, int lo = -1, int hi = -1, int lo2 = 0, int hi2 = 0) {
+static int launch_brick(SphContext* c, const SweepArgs& a) {
     // SPH_OPT_KERNEL_VARIANT: the instances of the two sweeps of the fused WCSPH step (include/sph_hip.h)
     const int var = c->opt_variant;
     if constexpr (MODE == GM_DENSITY_EOS) {
-        if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_EXACT>(c, lo, hi, lo2, hi2);
-        if ((var & SPH_VAR_GROUPS) && (var & SPH_VAR_MFMA)) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_MFMA>(c, lo, hi, lo2, hi2);
+        if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_EXACT>(c, a);
+        if ((var & SPH_VAR_GROUPS) && (var & SPH_VAR_MFMA)) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_MFMA>(c, a);
         // (pure_fluid is only ever set by a device-side check of THIS particle set: same count, single context)
         // ... or the HOST vouches that the whole scene holds no solid particle (SPH_OPT_PURE_FLUID_INSTANCE 2: a slab rank, whose
         // arrivals are never checked; every particle of such a scene keeps m_V = m_V0 bit for bit wherever it lives)
         const bool pure_checked = c->opt_pure_instance == 1 && c->pure_fluid && c->pure_fluid_n == c->N && !c->opt_drop_outside;
         if ((var & SPH_VAR_GROUPS) && c->uniform_state == 1 && (pure_checked || c->opt_pure_instance == 2))
-            return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_PURE_INTERNAL>(c, lo, hi, lo2, hi2);
-        if (var & SPH_VAR_GROUPS) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c, lo, hi, lo2, hi2);
+            return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_PURE_INTERNAL>(c, a);
+        if (var & SPH_VAR_GROUPS) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c, a);
     }
     if constexpr (MODE == GM_FORCE_FUSED_U) {
-        if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_EXACT>(c, lo, hi, lo2, hi2);
-        if (var & SPH_VAR_GAT_LDS) return launch_brick_cfg<MODE, CfgG3, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS>(c, lo, hi, lo2, hi2);
-        if (var & SPH_VAR_GAT_LDS4) return launch_brick_cfg<MODE, CfgG4, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS4>(c, lo, hi, lo2, hi2);
+        if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_EXACT>(c, a);
+        if (var & SPH_VAR_GAT_LDS) return launch_brick_cfg<MODE, CfgG3, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS>(c, a);
+        if (var & SPH_VAR_GAT_LDS4) return launch_brick_cfg<MODE, CfgG4, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS4>(c, a);
         switch (var & (SPH_VAR_FORCE_BF | SPH_VAR_DEEP)) {
-            case SPH_VAR_FORCE_BF: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF>(c, lo, hi, lo2, hi2);
-            case SPH_VAR_DEEP: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_DEEP>(c, lo, hi, lo2, hi2);
-            case SPH_VAR_FORCE_BF | SPH_VAR_DEEP: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF | SPH_VAR_DEEP>(c, lo, hi, lo2, hi2);
+            case SPH_VAR_FORCE_BF: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF>(c, a);
+            case SPH_VAR_DEEP: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_DEEP>(c, a);
+            case SPH_VAR_FORCE_BF | SPH_VAR_DEEP: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF | SPH_VAR_DEEP>(c, a);
             default: break;
         }
     }
     if constexpr (MODE == GM_FORCE_FUSED) {
-        if (var & SPH_VAR_DEEP) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_DEEP>(c, lo, hi, lo2, hi2);
+        if (var & SPH_VAR_DEEP) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_DEEP>(c, a);
     }
-    return launch_brick_cfg<MODE, Cfg0>(c, lo, hi, lo2, hi2);
+    return launch_brick_cfg<MODE, Cfg0>(c, a);
 }
 
 // what a brick sweep that was enqueued without error leaves behind (sph_derived.h)
 template <int MODE>
-static int sweep_done(SphContext* c, int rc) {
+static int sweep_done(SphContext* c, const SweepArgs& a, int rc) {
     if (rc) return rc;
     if (MODE == GM_DENSITY_EOS) sphd_lists_written(c->dv, c->uniform_state == 1 ? 1 : 0);
     if (MODE == GM_DF_DENSITY) sphd_lists_written(c->dv, 2);
-    if (mode_is_df_vdiv<MODE>() && c->df_collect) sphd_bpart_written(c->dv);  // every listed brick leaves its partial of the density error
+    if (mode_is_df_vdiv<MODE>() && a.collect_bpart) sphd_bpart_written(c->dv);  // every listed brick leaves its partial of the density error
     if (MODE == GM_DF_DENSITY_CHANGE) sphd_k_written(c->dv, 1);
     if (MODE == GM_DF_DENSITY_ADV) sphd_k_written(c->dv, 2);
     return 0;
 }
 
-// force sweep over the targets of x layers [lo, hi) only (slab mode: boundary layers first, interior later)
-int sphk_gather_layers(SphContext* c, int mode, int lo, int hi, int lo2, int hi2) {
-    if (c->N <= 0 || (hi <= lo && hi2 <= lo2)) return 0;
+// force sweep over the targets of x layers [lo, hi) u [lo2, hi2) only (slab mode: boundary layers first, interior later)
+int sphk_gather_layers(SphContext* c, int mode, const SweepArgs& args) {
+    if (c->N <= 0 || (args.hi <= args.lo && args.hi2 <= args.lo2)) return 0;
     if (c->opt_gather_impl == 1 && !brick_ok(c))
         return sph_fail(c, SPH_E_INVALID, "a slab rank needs the brick sweeps, and this context is beyond their reach (capacity > 16.7 M particles "
                                           "or more than 1000 cell layers in z): cut the domain into more slabs");
     if (mode != GM_FORCE_FUSED || c->opt_gather_impl == 0) return sph_fail(c, SPH_E_INVALID, "layer-restricted sweeps need the brick force kernel");
-    if (hi < lo) hi = lo;
-    if (c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, launch_brick<GM_FORCE_FUSED_U>(c, lo, hi, lo2, hi2));
-    return sweep_done<GM_FORCE_FUSED>(c, launch_brick<GM_FORCE_FUSED>(c, lo, hi, lo2, hi2));
+    SweepArgs a = args;
+    if (a.hi < a.lo) a.hi = a.lo;
+    if (c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
+    return sweep_done<GM_FORCE_FUSED>(c, a, launch_brick<GM_FORCE_FUSED>(c, a));
 }
 
 template <int MODE>
-static int launch_sweep(SphContext* c) {
+static int launch_sweep(SphContext* c, const SweepArgs& a) {
     if (c->N <= 0) return 0;
     if (c->opt_gather_impl == 0 || !brick_ok(c)) return launch_simple<MODE>(c, nullptr, c->N);
-    return sweep_done<MODE>(c, launch_brick<MODE>(c));
+    return sweep_done<MODE>(c, a, launch_brick<MODE>(c, a));
 }
 
 // DFSPH sweeps: one brick shape (the lists of GM_DF_DENSITY are read back by every later sweep of the step, so
 // writer and readers must agree on it); a list-reading sweep called while the lists are stale (positions moved
 // since the density sweep: only possible through the stand-alone API calls) takes the exact cell walk instead.
 template <int MODE>
-static int launch_df(SphContext* c) {
+static int launch_df(SphContext* c, const SweepArgs& a) {
     if (c->N <= 0) return 0;
     if (c->opt_gather_impl == 0 || !brick_ok(c) || (mode_reads_list<MODE>() && !sphd_lists_usable(c->dv))) {
         if (mode_is_df_vdiv<MODE>()) sphd_k_written(c->dv, 0);  // density_adv changes, the walk does not refresh k_j
@@ -1806,22 +1810,22 @@ static int launch_df(SphContext* c) {
     // group-sorted emission is worth as much to it: 0.333 -> 0.24 ms on the settled 1.75 M box (tools/list_reuse_probe.py had
     // timed it at the baseline emission's 0.333 against the WCSPH sweep's 0.245)
     if constexpr (MODE == GM_DF_DENSITY) {
-        if (c->opt_variant & SPH_VAR_GROUPS) return sweep_done<MODE>(c, launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c));
+        if (c->opt_variant & SPH_VAR_GROUPS) return sweep_done<MODE>(c, a, launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c, a));
     }
-    return sweep_done<MODE>(c, launch_brick_cfg<MODE, Cfg0>(c));
+    return sweep_done<MODE>(c, a, launch_brick_cfg<MODE, Cfg0>(c, a));
 }
 
-static int gather_dispatch(SphContext* c, int mode);
+static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a);
 
-int sphk_gather(SphContext* c, int mode) {
-    int rc = gather_dispatch(c, mode);
+int sphk_gather(SphContext* c, int mode, const SweepArgs& a) {
+    int rc = gather_dispatch(c, mode, a);
     // sweeps that scatter two-way coupling reactions (WCSPH.py:66-68, DFSPH.py:313, 389-390) are followed by the fold
     if (!rc && c->n_dyn_host != 0 && (mode == GM_PRESSURE || mode == GM_FORCE_FUSED || mode == GM_DF_DIV_ITER || mode == GM_DF_PRESSURE_ITER))
         rc = sphk_fold_coupling(c);
     return rc;
 }
 
-static int gather_dispatch(SphContext* c, int mode) {
+static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a) {
     // every sweep but the fused step's own pair reads or rewrites density / pressure in aux
     if (sphd_aux_in_eos2(c->dv) && mode != GM_DENSITY_EOS && mode != GM_FORCE_FUSED && mode != GM_BVOL_STATIC && mode != GM_BVOL_DYNAMIC) {
         int rc = sph_ensure_aux(c);
@@ -1837,29 +1841,29 @@ static int gather_dispatch(SphContext* c, int mode) {
             SPH_LAUNCH_CHECK(c);
             return 0;
         }
-        case GM_DENSITY: return launch_sweep<GM_DENSITY>(c);
-        case GM_DENSITY_EOS: return launch_sweep<GM_DENSITY_EOS>(c);
-        case GM_NONPRESSURE: return launch_sweep<GM_NONPRESSURE>(c);
-        case GM_PRESSURE: return launch_sweep<GM_PRESSURE>(c);
+        case GM_DENSITY: return launch_sweep<GM_DENSITY>(c, a);
+        case GM_DENSITY_EOS: return launch_sweep<GM_DENSITY_EOS>(c, a);
+        case GM_NONPRESSURE: return launch_sweep<GM_NONPRESSURE>(c, a);
+        case GM_PRESSURE: return launch_sweep<GM_PRESSURE>(c, a);
         case GM_FORCE_FUSED:
             // one gather per pair when every fluid particle has the same mass (and the density sweep of this step
             // left its stg / gat records): see SPH_OPT_UNIFORM_FLUID
             if (c->uniform_state == 1 && c->opt_gather_impl == 1 && brick_ok(c) && sphd_one_gather_wcsph(c->dv) && c->N > 0)
-                return sweep_done<GM_FORCE_FUSED_U>(c, launch_brick<GM_FORCE_FUSED_U>(c));
-            return launch_sweep<GM_FORCE_FUSED>(c);
-        case GM_DF_DENSITY: return launch_df<GM_DF_DENSITY>(c);
-        case GM_DF_FACTOR: return launch_df<GM_DF_FACTOR>(c);
-        case GM_DF_DENSITY_CHANGE: return launch_df<GM_DF_DENSITY_CHANGE>(c);
-        case GM_DF_DENSITY_ADV: return launch_df<GM_DF_DENSITY_ADV>(c);
+                return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
+            return launch_sweep<GM_FORCE_FUSED>(c, a);
+        case GM_DF_DENSITY: return launch_df<GM_DF_DENSITY>(c, a);
+        case GM_DF_FACTOR: return launch_df<GM_DF_FACTOR>(c, a);
+        case GM_DF_DENSITY_CHANGE: return launch_df<GM_DF_DENSITY_CHANGE>(c, a);
+        case GM_DF_DENSITY_ADV: return launch_df<GM_DF_DENSITY_ADV>(c, a);
         // Jacobi sweeps: with the lists, the sign-coded staging records and k_j = b_j * factor_j all current (the
         // solver loops inside the library keep them so), the neighbour costs one 4-byte gather instead of two records
         case GM_DF_DIV_ITER:
-            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 1)) return launch_df<GM_DF_DIV_ITER_U>(c);
-            return launch_df<GM_DF_DIV_ITER>(c);
+            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 1)) return launch_df<GM_DF_DIV_ITER_U>(c, a);
+            return launch_df<GM_DF_DIV_ITER>(c, a);
         case GM_DF_PRESSURE_ITER:
-            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 2)) return launch_df<GM_DF_PRESSURE_ITER_U>(c);
-            return launch_df<GM_DF_PRESSURE_ITER>(c);
-        case GM_DF_NONPRESSURE: return launch_df<GM_DF_NONPRESSURE>(c);
+            if (c->opt_gather_impl == 1 && sphd_one_gather_df(c->dv, 2)) return launch_df<GM_DF_PRESSURE_ITER_U>(c, a);
+            return launch_df<GM_DF_PRESSURE_ITER>(c, a);
+        case GM_DF_NONPRESSURE: return launch_df<GM_DF_NONPRESSURE>(c, a);
     }
     return sph_fail(c, SPH_E_INVALID, "unknown gather mode");
 }

@@ -98,15 +98,13 @@ struct SphContext {
     hipEvent_t ev_off;   // recorded behind those copies
     hipEvent_t ev_pack;  // recorded behind the halo packers of sph_slab_forces
     hipEvent_t ev_fork;  // main stream -> side stream hand-off in sph_slab_forces
-    hipStream_t side;    // slab mode: boundary force sweep + halo packers run here, concurrently with the interior sweep
-    bool use_side;       // launchers enqueue on `side` (with their own brick list) while this is set
+    hipStream_t side;    // slab mode: boundary force sweep + halo packers run here (SweepArgs::side), concurrently with the interior sweep
     int2* brick_list2;   // [brick_cap] brick list of launches on the side stream
     int* brick_count2;
     int off_zero_mask;   // which of the pending offsets are layer 0 (no copy needed)
-    int off_stamp;       // stamp of the last sort that delivered layer offsets (h_pinned[17] shows it once they are there)
+    int off_stamp;       // stamp of the last sort that delivered layer offsets itself (sphk_sort_scatter's deliver_offsets: no launch
+                         // of their own); h_pinned[17] shows it once they are there
     bool off_stamp_pending;  // sph_layer_offsets_end waits for the stamp (spinning on mapped memory), not for ev_off
-    bool off_in_sort;    // sph_slab_advance: the sort that follows delivers the layer offsets itself (k_unstable_place reads the
-    CellIdx16 off_ix;    //   scanned cells into the mapped buffer and ev_off is recorded right behind it) -- no launch of their own
     int tgt_layers[4];  // density lo/hi, force lo/hi (slab mode); default 0..nx
     int nx_alloc;       // grid_num[0] at sph_create: what the cell arrays and brick lists are sized for (sph_slab_set_window)
     int in_off;  // first live record of the current set (non-zero only between sph_select_range and the next sort)
@@ -163,7 +161,6 @@ struct SphContext {
     hipEvent_t ev_df[4];
     double* df_part;    // [SPH_DF_ERR_BLOCKS] per-workgroup partial sums
     double* df_bpart;   // [brick_cap] per-BRICK partial sums of the density error, written by the refresh sweep of a solver iteration (SPH_OPT_DF_FUSE_ERROR)
-    int df_collect;     // the sweep being enqueued is such a refresh sweep (sph_view hands df_bpart to the kernel)
     int opt_df_fuse_err;  // SPH_OPT_DF_FUSE_ERROR (default 1)
     SphDfsphParams df;  // DFSPH solver knobs
     SphDfsphStats df_stats;
@@ -178,8 +175,6 @@ struct SphContext {
     int opt_rigid_x0;     // SPH_OPT_RIGID_SUMS_FROM_X0: the rest-cm sums read x_0 (set by the host around the rest cm of a restart)
     int opt_pure_instance;  // SPH_OPT_PURE_FLUID_INSTANCE: 1 (default) = a solid-free single context may run the pure-fluid density instance
     int opt_variant;     // SPH_OPT_KERNEL_VARIANT (bit mask of SPH_VAR_*)
-    int fuse_advect;     // set around the force launch of sph_step when the advect can ride in its finish
-    int skip_acc;        // set by sph_step for every step but the last of a call: the fused force finish keeps its acceleration to itself
     bool acc_partial;    // sph_slab_forces with the interior advect fused: the interior targets' accelerations were consumed in the
                          // force finish and never written out; sph_download(ACCELERATION) refuses until something writes them all
     int opt_uniform;     // SPH_OPT_UNIFORM_FLUID: -1 auto, 0 off, 1 check once
@@ -203,7 +198,6 @@ struct SphContext {
 };
 
 DevView sph_view(const SphContext* c);
-static inline hipStream_t sph_stream(const SphContext* c) { return c->use_side ? c->side : c->stream; }
 #define SPH_BRICK_HEAVY 160  // targets from which a brick counts as heavy (a full 4x2x4 brick at rest has 256)
 // particle positions / order / flags changed: neighbour lists and the non-empty-brick list are stale
 static inline void sph_invalidate_lists(SphContext* c) { sphd_invalidate(c->dv); }
@@ -234,15 +228,24 @@ int sph_check_device_flags(SphContext* c);
 // ---- launch entry points implemented in the .hip files --------------------
 int sphk_hash_histogram(SphContext* c);
 int sphk_scan(SphContext* c);
-int sphk_sort_scatter(SphContext* c, bool sort_acc);
+int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets);  // non-null: the place kernel also hands these scanned cells to the host
 int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, double* out);
 int sphk_rigid_apply16(SphContext* c, int object_id, const double* sums, int mode);
 int sphk_scatter_rest(SphContext* c, const int* pid_dev, const float* x0_dev, int n);
 struct BrickListArgs;
 int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a, SphPartKey* key);  // sph_gather.hip: what the sort's place kernel needs to build the step's brick list, and the key it will serve
-int sphk_gather(SphContext* c, int mode);
-int sphk_gather_layers(SphContext* c, int mode, int lo, int hi, int lo2, int hi2);  // brick sweep, targets in x layers [lo,hi) u [lo2,hi2)
-int sphk_pack_advected(SphContext* c, int first, int count, void* dst);
+// What ONE sweep launch is told beyond its mode.  The default value is the plain sweep: the mode's own targets, nothing fused,
+// the acceleration stored, on the main stream.
+struct SweepArgs {
+    int lo = -1, hi = -1, lo2 = 0, hi2 = 0;  // targets in x layers [lo, hi) u [lo2, hi2); lo < 0: the mode's default from tgt_layers
+    bool fuse_advect = false;    // GM_FORCE_FUSED_U: the finish also integrates its fluid targets (DevView::fuse_advect)
+    bool store_acc = true;       // false (with fuse_advect only): the finish keeps the acceleration it has just consumed to itself
+    bool collect_bpart = false;  // the refresh sweep of a DFSPH solver iteration: every brick leaves its density-error partial in df_bpart
+    bool side = false;           // enqueue on the side stream, over a private brick list (slab mode: the boundary force sweep)
+};
+int sphk_gather(SphContext* c, int mode, const SweepArgs& a = SweepArgs());
+int sphk_gather_layers(SphContext* c, int mode, const SweepArgs& a);  // force sweep over the targets of a.lo .. a.hi2 only (slab mode)
+int sphk_pack_advected(SphContext* c, int first, int count, void* dst, hipStream_t st);
 int sphk_eos(SphContext* c);
 int sph_ensure_aux(SphContext* c);  // materialise density / pressure in aux if the lean density finish left them in eos2
 int sphk_stats(SphContext* c, SphStats* out);  // synchronises
@@ -255,7 +258,7 @@ int sphk_df_predict_velocity(SphContext* c);
 int sphk_df_advect(SphContext* c, bool fused_fluid_walls);
 int sphk_advect(SphContext* c, bool fused_fluid_walls);
 int sphk_advect_dyn_list(SphContext* c);  // dynamic rigid particles only
-int sphk_fold_coupling_range(SphContext* c, int first, int count);  // ... of a record range, on the current sweep stream
+int sphk_fold_coupling_range(SphContext* c, int first, int count, hipStream_t st);  // ... of a record range, on the stream of the sweep it follows
 int sphk_fold_coupling(SphContext* c);    // acc of the dynamic rigid particles += their fixed-point reaction sums (which are zeroed)
 int sphk_advect_range(SphContext* c, int first, int count);
 int sphk_enforce_boundary(SphContext* c, int particle_type);

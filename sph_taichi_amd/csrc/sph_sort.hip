@@ -248,7 +248,7 @@ int sphk_scan(SphContext* c) {
     return 0;
 }
 
-int sphk_sort_scatter(SphContext* c, bool sort_acc) {
+int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets) {
     if (c->N <= 0) return 0;
     DevView d = sph_view(c);
     const int nb = (c->N + TPB - 1) / TPB;
@@ -265,11 +265,9 @@ int sphk_sort_scatter(SphContext* c, bool sort_acc) {
     CellIdx16 off_ix;
     int* off_out = nullptr;
     for (int k = 0; k < 16; ++k) off_ix.v[k] = -1;
-    if (c->off_in_sort) {
-        off_ix = c->off_ix;
+    if (deliver_offsets) {
+        off_ix = *deliver_offsets;
         SPH_HIP(c, hipHostGetDevicePointer((void**)&off_out, c->h_pinned, 0));
-    }
-    if (c->off_in_sort) {
         c->off_stamp = c->off_stamp == 0x7fffffff ? 1 : c->off_stamp + 1;
         c->off_stamp_pending = true;
     }
