@@ -532,6 +532,44 @@ int32_t sph_kinematic_apply(SphContext* ctx, const SphBodyPose* poses, int32_t n
 int32_t sph_get_time(SphContext* ctx, double* t);
 int32_t sph_set_time(SphContext* ctx, double t);
 
+/* ======================================================================================
+ * Flow diagnostics (the reference's older engine prints max velocity / acceleration / density / pressure from whole-array
+ * downloads every step and sets dt from them; its current engine has neither): ONE streaming reduction over the live
+ * records in their current order -- 64 bytes read per particle, nothing written but the rows -- per object and over
+ * all particles.  Row k < n_objects collects the particles whose object id is k (indexed as rigid_rest_cm is); the LAST
+ * row, n_objects, collects every particle, those whose object id names no object included.
+ * "fluid" = material fluid; "moving" = fluid or is_dynamic: the particles advect integrates.
+ * The values are those sph_download would return at that moment: density / pressure that a fused step left in its own
+ * record are materialised first (as any download of them does); nothing else of the context is written, and a run with
+ * diagnostics calls between its steps ends bit-identical to the run without.  While sph_download of the acceleration
+ * refuses (after sph_slab_forces), sph_diag_reduce answers SPH_E_STATE for the same reason.
+ * DETERMINISTIC: sums are f64, grouped in a fixed order (lane -> wave -> block -> row; csrc/sph_diag.hip) that depends on
+ * the particle count and order alone, never on scheduling: two calls on one state return the same bits.
+ * sph_diag_reduce enqueues two launches on the context's stream (grid: at most SPH_DIAG_BLOCKS blocks of SPH_DIAG_THREADS,
+ * striding over the records); sph_diag_download copies the rows of the LAST reduce and synchronises -- SPH_E_STATE if there
+ * was none, SPH_E_INVALID unless n_rows == n_objects + 1.  More than SPH_DIAG_MAX_OBJECTS objects: SPH_E_INVALID (the
+ * per-block row table lives in LDS).  Single-domain contexts only: a slab rank, whose ghost records would be counted
+ * twice, answers SPH_E_STATE.
+ * ==================================================================================== */
+#define SPH_DIAG_BLOCKS 1024
+#define SPH_DIAG_THREADS 256
+#define SPH_DIAG_MAX_OBJECTS 96
+typedef struct SphDiagRow {
+    int64_t count;              /* particles of the row */
+    int64_t fluid_count;        /* of those, fluid */
+    int64_t moving_count;       /* of those, fluid or is_dynamic */
+    double mass;                /* sum m */
+    double mx[3];               /* sum m x: / mass = centre of mass; -g . mx = potential energy */
+    double momentum[3];         /* sum m v */
+    double kinetic;             /* sum 1/2 m |v|^2 */
+    double v2_max;              /* max |v|^2 over the row, formed in f64 from the f32 components */
+    double a2_max;              /* max |a|^2 over the row's moving particles; 0 if there are none */
+    float density_min, density_max, pressure_min, pressure_max;   /* over the row's fluid particles; 0 if there are none */
+    float lo[3], hi[3];         /* axis-aligned bounds of x over the row; 0 if it is empty */
+} SphDiagRow;
+int32_t sph_diag_reduce(SphContext* ctx);                                     /* enqueues */
+int32_t sph_diag_download(SphContext* ctx, SphDiagRow* rows, int32_t n_rows); /* n_rows == n_objects + 1; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

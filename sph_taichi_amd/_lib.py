@@ -77,6 +77,18 @@ class SphBodyPose(C.Structure):
 
 MAX_KINEMATIC = 8
 
+
+class SphDiagRow(C.Structure):
+    """Mirror of `struct SphDiagRow` (include/sph_hip.h)."""
+    _fields_ = [("count", C.c_int64), ("fluid_count", C.c_int64), ("moving_count", C.c_int64), ("mass", C.c_double),
+                ("mx", _D3), ("momentum", _D3), ("kinetic", C.c_double), ("v2_max", C.c_double), ("a2_max", C.c_double),
+                ("density_min", C.c_float), ("density_max", C.c_float), ("pressure_min", C.c_float),
+                ("pressure_max", C.c_float), ("lo", _F3), ("hi", _F3)]
+
+
+# launch shape of the diagnostics reduction (SPH_DIAG_BLOCKS x SPH_DIAG_THREADS, striding) and its object limit
+DIAG_BLOCKS, DIAG_THREADS, DIAG_MAX_OBJECTS = 1024, 256, 96
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -186,6 +198,8 @@ SYMBOLS = [
     ("sph_kinematic_apply", C.c_int32, [_ctx, C.POINTER(SphBodyPose), C.c_int32]),
     ("sph_get_time", C.c_int32, [_ctx, C.POINTER(C.c_double)]),
     ("sph_set_time", C.c_int32, [_ctx, C.c_double]),
+    ("sph_diag_reduce", C.c_int32, [_ctx]),
+    ("sph_diag_download", C.c_int32, [_ctx, C.POINTER(SphDiagRow), C.c_int32]),
 ]
 
 _LIB = None

@@ -82,6 +82,7 @@ struct DevView {
 };
 
 struct SphRender;   // frame export (sph_render.hip): camera, invisible set, key / image / depth buffers; null until sph_render_set_params
+struct SphDiag;     // flow diagnostics (sph_diag.hip): per-block partial rows and the result rows; null until sph_diag_reduce
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -188,6 +189,7 @@ struct SphContext {
     bool slab_ev_open;  // slab mode: events [0..2] of ev[ev_used] are recorded, [3..4] follow in sph_slab_forces
     SphTimings tm;
     SphRender* render;
+    SphDiag* diag;
     // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
     double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
@@ -272,6 +274,7 @@ int sphk_rest_records(SphContext* c, float4* dst);
 int sphk_kinematic_apply(SphContext* c, const KinPoses& poses);
 int sphk_insert(SphContext* c, int field, const void* src);
 void sph_render_release(SphContext* c);  // sph_render.hip: frees the frame-export buffers (sph_destroy)
+void sph_diag_release(SphContext* c);    // sph_diag.hip: frees the diagnostics rows (sph_destroy)
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -405,6 +405,19 @@ class ParticleSystem:
                 R, c, _, _ = _motion.pose(m, t)
                 obj["mesh"].vertices = c + (np.asarray(obj["restPosition"], dtype=np.float64) - m.pivot) @ R.T
 
+    # ---- flow diagnostics and the CFL-governed time step (diagnostics.py, timestep.py) ------
+    def diagnostics(self):
+        """Counts, mass, centre of mass, momentum, energies, max |v| / |a|, density / pressure extrema and bounds, per
+        object and over all particles, of the state as it is now: one reduction on the device behind whatever was
+        enqueued; only the rows are copied back (synchronises).  Changes nothing a later step reads."""
+        from . import diagnostics as _diag
+        return _diag.reduce(self)
+
+    def build_time_step_controller(self, solver):
+        """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""
+        from . import timestep as _timestep
+        return _timestep.build_controller(self, solver)
+
     # ---- state checkpoint (SURVEY 8 f3; the reference has none) ----------------------
     _STATE_FIELDS = ("object_id", "x", "x_0", "v", "acceleration", "m_V", "m", "density", "pressure", "material",
                      "color", "is_dynamic", "pid")

@@ -11,10 +11,16 @@ frames optional ASCII-PLY particle export (`exportPly`), OBJ rigid-body export
 (`exportObj`) and PNG frame export (`exportFrame`, without the objects listed in
 `invisibleObjects`), written where the reference writes them.  `--timing` prints the
 per-phase HIP-event breakdown (sort / neighbour / force / integrate).
+
+A scene whose Configuration holds an "adaptiveTimeStep" object gets its dt from the CFL criteria of timestep.py, once per
+frame (one reduction on the device and one host synchronisation; dt never changes inside a frame's steps).
+`--diagnostics PATH` writes one JSON line per exported interval: frame, time, dt and the all-particle diagnostics row.
+`output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import os
 import time
@@ -43,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dump_npz", default="", help="write the final per-particle state here")
     ap.add_argument("--save_state", default="", help="write a restartable checkpoint (.npz) after the last frame")
     ap.add_argument("--load_state", default="", help="continue from a checkpoint written by --save_state")
+    ap.add_argument("--diagnostics", default="", metavar="PATH",
+                    help="write one JSON line per exported interval here: frame, time, dt, the all-particle diagnostics row")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
                     help="size of the exportFrame images (the reference's window is 1024 x 1024)")
     ap.add_argument("--camera", type=float, nargs=6, default=None, metavar=("EX", "EY", "EZ", "LX", "LY", "LZ"),
@@ -83,12 +91,19 @@ def main(argv=None):
         print(f"restored {args.load_state} (frames done: {int(meta.get('frames', 0))})")
     if args.timing:
         ps.set_option(_lib.OPT_TIMING, 1)
+    controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
+    diag_out = open(args.diagnostics, "w") if args.diagnostics else None
 
     cnt = cnt_ply = frames_written = 0
     render_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
         solver.step(substeps)
+        diag = controller.update()[1] if controller is not None else None     # dt of the NEXT frame's steps
+        if diag_out is not None and cnt % output_interval == 0:
+            diag = diag if diag is not None else ps.diagnostics()
+            diag_out.write(json.dumps({"frame": cnt, "time": diag.time, "dt": float(np.float32(solver.dt[None])),
+                                       "total": diag.total.as_dict()}) + "\n")
         if output_frames and cnt % output_interval == 0:
             ps.sync()                          # the frame's cost, not the steps still in flight before it
             tr = time.perf_counter()
@@ -113,6 +128,13 @@ def main(argv=None):
     steps = args.frames * substeps
     report = {"scene": scene_name, "particles": ps.particle_max_num, "steps": steps,
               "steps_per_s": round(steps / dt, 2), "ms_per_step": round(dt / steps * 1e3, 4)}
+    sim_time = C.c_double()
+    ps._call("sph_get_time", C.byref(sim_time))            # the context's clock: the sum of the dt of every step made
+    report["sim_time"] = sim_time.value
+    if controller is not None:
+        report["dt_min_used"], report["dt_max_used"] = controller.dt_min_used, controller.dt_max_used
+    if diag_out is not None:
+        diag_out.close()
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
