@@ -160,8 +160,10 @@ enum SphOption {
                                   take the displaced body's centre for the rest centre.  The Python layer sets it around the
                                   rest-cm computation of a restarted ParticleSystem and clears it again; default 0. */
     SPH_OPT_PURE_FLUID_INSTANCE = 15 /* 1 (default) = a single context found (on the device) to hold no solid particle at all runs the
-                                  density sweep's pure-fluid instance (m_V_j = m_V0 from a register; bit-identical results);
-                                  0 = always the general instance (the A/B switch; was the SPH_DISABLE_PURE_FLUID environment
+                                  pure-fluid instances of the uniform-fluid step's two sweeps: density (m_V_j = m_V0 from a register)
+                                  and one-gather force (the branch-free pair term without its solid-neighbour path).  Both issue fewer
+                                  instructions for the same operations on the same operands: bit-identical results;
+                                  0 = always the general instances (the A/B switch; was the SPH_DISABLE_PURE_FLUID environment
                                   variable in ABI 4); 2 = the CALLER vouches that the whole scene holds no solid particle at all
                                   (slab ranks: arrivals are never checked on the device; the Python layer sets it when the scene
                                   file has no rigid block and no rigid body) */,

@@ -132,7 +132,8 @@ __device__ __forceinline__ float4 target_load_E(const DevView& d, int i) {
     return make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-template <int MODE, bool EXACT = false>
+// SOLIDS = false (the pure-fluid instance of the one-gather force sweep): what only a solid neighbour's term reads stays 0
+template <int MODE, bool EXACT = false, bool SOLIDS = true>
 __device__ __forceinline__ void target_init(const DevView& d, Target& t, const float4 A, const float4 B, const float4 E) {
     t.x = A.x; t.y = A.y; t.z = A.z; t.mV = A.w;
     t.vx = B.x; t.vy = B.y; t.vz = B.z;
@@ -158,7 +159,7 @@ __device__ __forceinline__ void target_init(const DevView& d, Target& t, const f
         t.p = E.x; t.rho = E.y; t.m = d.m_u;
         t.dpi = EXACT ? __fdiv_rn(E.x, E.y * E.y) : E.x * __builtin_amdgcn_rcpf(E.y * E.y);
         t.st_c = (d.sigma / d.m_u) * d.m_u;  // (sigma / m_i) * m_j with the common mass (WCSPH.py:100)
-        t.dpj_solid = t.p / (d.rho0 * d.rho0);
+        if (SOLIDS) t.dpj_solid = t.p / (d.rho0 * d.rho0);
     }
     if (MODE == GM_BVOL_STATIC || MODE == GM_BVOL_DYNAMIC) t.s0 = d.w_zero;  // sph_base.py:95, 110
     t.nn = 0;
@@ -384,6 +385,11 @@ __device__ __forceinline__ ForceK force_k(const DevView& d) {
     K.cpk = -d.rho0 * d.m_V0;
     return K;
 }
+// PURE (SPH_VAR_PURE_INTERNAL: the context holds no solid particle at all, see sph_pure_fluid_instances): every neighbour is a
+// fluid particle, so the fluid term stands alone -- no compare on A.w with its exec-mask save / restore / branch, no solid body
+// (accept test, dependent aux load, 64-bit atomics), and gj / not_self, which only that body read, are dead.  The fluid term is
+// the SAME expression tree on the same operand values: results are bit-identical to the general instance.
+template <bool PURE = false>
 __device__ __forceinline__ void pair_force_u_bf(const DevView& d, const ForceK& K, Target& t, float rx, float ry, float rz, float r2,
                                                 const float4 A, const float4 B, int gj, bool not_self) {
     const float rinv = __builtin_amdgcn_rsqf(r2 + 1e-30f);
@@ -395,7 +401,7 @@ __device__ __forceinline__ void pair_force_u_bf(const DevView& d, const ForceK& 
     const float f2 = f * f, u2 = u * u;
     const float cg = K.kg * (4.0f * u2 - f2);   // (k_dw / h) (4 u^2 - t^2)
     const float gc = rn > 1e-5f ? cg * rinv : 0.0f;
-    if (A.w > 0.0f) {
+    if (PURE || A.w > 0.0f) {
         const float wq = K.kw2 * (f2 * f) - K.kw8 * (u2 * u);
         const float w = (r2 > K.d2) ? wq : K.w_d;
         const float c = t.st_c * w;                                               // WCSPH.py:93-102
@@ -833,6 +839,10 @@ __global__ __launch_bounds__(TPB, (brick_waves_per_simd<MODE, VAR>())) void k_ga
     // bit-identical, unlike a form that would scale the sum of W once).  Chosen by the launcher, not a user-visible bit.
     constexpr bool V_PURE = (VAR & SPH_VAR_PURE_INTERNAL) != 0 && MODE == GM_DENSITY_EOS;
     constexpr bool V_BF = (VAR & SPH_VAR_FORCE_BF) != 0 && MODE == GM_FORCE_FUSED_U;
+    // ... and the counterpart in the one-gather force sweep: no neighbour is a solid, so the branch-free pair term drops the solid
+    // path (pair_force_u_bf<true>) and every target is a fluid particle with m_V = m_V0.  Instruction count only: the sums are the
+    // general instance's, operation for operation.  (The exact-math instance and the per-target cell walk keep their general form.)
+    constexpr bool V_PUREF = (VAR & SPH_VAR_PURE_INTERNAL) != 0 && V_BF;
     constexpr bool V_DEEP = (VAR & SPH_VAR_DEEP) != 0 && mode_reads_list<MODE>();
     // SPH_VAR_GAT_LDS / _LDS4 (round 6, VERDICT r05 "next" #5): the neighbour's second record (gat: v, p / rho^2) staged in LDS beside
     // the first instead of gathered through the L1 -- the counters say the force sweep's vector-memory path is busy with TAG
@@ -1067,13 +1077,13 @@ __global__ __launch_bounds__(TPB, (brick_waves_per_simd<MODE, VAR>())) void k_ga
         if (MODE == GM_FORCE_FUSED_U && !overflow) {
             if (li >= sColS[col]) {
                 Ai = sQ[li];
-                Ai.w = Ai.w > 0.0f ? d.m_V0 : -Ai.w;  // U = m / rho_raw of a fluid particle (whose m_V is m_V0 on this path), -m_V of a solid one
+                Ai.w = (V_PUREF || Ai.w > 0.0f) ? d.m_V0 : -Ai.w;  // U = m / rho_raw of a fluid particle (whose m_V is m_V0 on this path), -m_V of a solid one
             } else {
                 Ai = d.xm[gi];  // a target in flat cell 0: its own range is never staged (the max(0, idx-1) quirk, step A)
             }
         }
         Target t;
-        target_init<MODE, V_EXACT>(d, t, Ai, Bi, Ei);
+        target_init<MODE, V_EXACT, !V_PUREF>(d, t, Ai, Bi, Ei);
         const bool g = valid && target_gathers<MODE>(t.flags);
         bool walk = g && overflow;
         int cnt = 0;
@@ -1438,6 +1448,7 @@ __global__ __launch_bounds__(TPB, (brick_waves_per_simd<MODE, VAR>())) void k_ga
                 const float rz = HAS_W ? fmaf(0.5f, s_.A.z, tzl) : t.z - s_.A.z;
                 const float r2 = rx * rx + ry * ry + rz * rz;
                 if (V_EXACT) { pair_force_u_exact(d, t, rx, ry, rz, r2, s_.A, s_.B, s_.g, s_.j != li); return; }
+                if (V_PUREF) { pair_force_u_bf<true>(d, FK, t, rx, ry, rz, r2, s_.A, s_.B, 0, true); return; }
                 if (V_BF) { pair_force_u_bf(d, FK, t, rx, ry, rz, r2, s_.A, s_.B, s_.g, s_.j != li); return; }
                 const float rinv = sph_rsq(r2);
                 const float rn = r2 * rinv;
@@ -1737,11 +1748,8 @@ static int launch_brick(SphContext* c, const SweepArgs& a) {
     if constexpr (MODE == GM_DENSITY_EOS) {
         if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_EXACT>(c, a);
         if ((var & SPH_VAR_GROUPS) && (var & SPH_VAR_MFMA)) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_MFMA>(c, a);
-        // (pure_fluid is only ever set by a device-side check of THIS particle set: same count, single context)
-        // ... or the HOST vouches that the whole scene holds no solid particle (SPH_OPT_PURE_FLUID_INSTANCE 2: a slab rank, whose
-        // arrivals are never checked; every particle of such a scene keeps m_V = m_V0 bit for bit wherever it lives)
-        const bool pure_checked = c->opt_pure_instance == 1 && c->pure_fluid && c->pure_fluid_n == c->N && !c->opt_drop_outside;
-        if ((var & SPH_VAR_GROUPS) && c->uniform_state == 1 && (pure_checked || c->opt_pure_instance == 2))
+        // (the rule that admits the pure-fluid instances: sph_pure_fluid_instances, sph_internal.h)
+        if ((var & SPH_VAR_GROUPS) && sph_pure_fluid_instances(c))
             return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS | SPH_VAR_PURE_INTERNAL>(c, a);
         if (var & SPH_VAR_GROUPS) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_GROUPS>(c, a);
     }
@@ -1749,6 +1757,9 @@ static int launch_brick(SphContext* c, const SweepArgs& a) {
         if (c->opt_exact_math) return launch_brick_cfg<MODE, Cfg0, SPH_VAR_EXACT>(c, a);
         if (var & SPH_VAR_GAT_LDS) return launch_brick_cfg<MODE, CfgG3, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS>(c, a);
         if (var & SPH_VAR_GAT_LDS4) return launch_brick_cfg<MODE, CfgG4, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_GAT_LDS4>(c, a);
+        // the pure-fluid instance of the default force loop, under the rule that admits the density sweep's
+        if ((var & (SPH_VAR_FORCE_BF | SPH_VAR_DEEP)) == (SPH_VAR_FORCE_BF | SPH_VAR_DEEP) && sph_pure_fluid_instances(c))
+            return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF | SPH_VAR_DEEP | SPH_VAR_PURE_INTERNAL>(c, a);
         switch (var & (SPH_VAR_FORCE_BF | SPH_VAR_DEEP)) {
             case SPH_VAR_FORCE_BF: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_FORCE_BF>(c, a);
             case SPH_VAR_DEEP: return launch_brick_cfg<MODE, Cfg0, SPH_VAR_DEEP>(c, a);

@@ -28,7 +28,7 @@
 #define SPH_MAX_TIMED_STEPS 128
 #define SPH_GLIST_ROWS 96  // list entries allocated per particle (24 groups of four); lists up to LISTCAP = 95 entries (developed dam-break flows reach 58, profiles/archive/r03i)
 #define SPH_DF_ERR_BLOCKS 512
-#define SPH_VAR_PURE_INTERNAL 64   // not a user bit (sph_set_option refuses masks above 63): the pure-fluid instance of the density sweep
+#define SPH_VAR_PURE_INTERNAL 64   // not a user bit (sph_set_option refuses masks above 63): the pure-fluid instances of the density sweep and of the one-gather force sweep
 #define SPH_VAR_DEFAULT (SPH_VAR_GROUPS | SPH_VAR_FORCE_BF | SPH_VAR_DEEP)  // SPH_OPT_KERNEL_VARIANT when the caller does not choose: the fastest rows of profiles/archive/r03f_variants_partition_x_emission.json (density) and r02g_variants_force.json (force)
 
 struct DevView {
@@ -174,7 +174,7 @@ struct SphContext {
     int opt_df_runahead;  // SPH_OPT_DF_RUNAHEAD: 1 = DFSPH solver bodies are enqueued one ahead of the convergence test
     int opt_exact_math;   // SPH_OPT_EXACT_MATH: 1 = IEEE divide / sqrt instances of the brick sweeps (A/B of the fast-math choice)
     int opt_rigid_x0;     // SPH_OPT_RIGID_SUMS_FROM_X0: the rest-cm sums read x_0 (set by the host around the rest cm of a restart)
-    int opt_pure_instance;  // SPH_OPT_PURE_FLUID_INSTANCE: 1 (default) = a solid-free single context may run the pure-fluid density instance
+    int opt_pure_instance;  // SPH_OPT_PURE_FLUID_INSTANCE: 1 (default) = a solid-free single context may run the pure-fluid instances (density, one-gather force)
     int opt_variant;     // SPH_OPT_KERNEL_VARIANT (bit mask of SPH_VAR_*)
     bool acc_partial;    // sph_slab_forces with the interior advect fused: the interior targets' accelerations were consumed in the
                          // force finish and never written out; sph_download(ACCELERATION) refuses until something writes them all
@@ -211,6 +211,16 @@ static inline bool sph_is_slab(const SphContext* c) {
 }
 // the particle SET changed (records appended / dropped / re-selected): whatever a device-side check established about it is void
 static inline void sph_forget_pure_fluid(SphContext* c) { c->pure_fluid = 0; c->pure_fluid_n = -1; }
+// May the sweeps of the uniform-fluid step run their pure-fluid instances?  ONE rule for both (density + EOS, one-gather force):
+// the device-side check found no solid among exactly the particles the context holds now (pure_fluid is only ever set by a check
+// of THIS particle set: same count, single context), or the HOST vouches that the whole scene holds no solid particle
+// (SPH_OPT_PURE_FLUID_INSTANCE 2: a slab rank, whose arrivals are never checked; every particle of such a scene keeps
+// m_V = m_V0 bit for bit wherever it lives).  Whatever changes the particle set forgets the verdict (sph_forget_pure_fluid),
+// an upload of material / m / m_V asks for a new check (uniform_state = -1), SPH_OPT_PURE_FLUID_INSTANCE 0 is the A/B switch.
+static inline bool sph_pure_fluid_instances(const SphContext* c) {
+    const bool pure_checked = c->opt_pure_instance == 1 && c->pure_fluid && c->pure_fluid_n == c->N && !c->opt_drop_outside;
+    return c->uniform_state == 1 && (pure_checked || c->opt_pure_instance == 2);
+}
 // after a host synchronisation: did a device-side error flag rise since the last look (k_scan_fused's bounded wait)?  Marks the
 // sort invalid and returns SPH_E_STATE with the message set; 0 otherwise.
 int sph_check_device_flags(SphContext* c);
