@@ -572,6 +572,49 @@ typedef struct SphDiagRow {
 int32_t sph_diag_reduce(SphContext* ctx);                                     /* enqueues */
 int32_t sph_diag_download(SphContext* ctx, SphDiagRow* rows, int32_t n_rows); /* n_rows == n_objects + 1; synchronises */
 
+/* ======================================================================================
+ * Depth-integrated column maps (no reference counterpart: the quantities a dam-break run is compared on -- wave gauges,
+ * depth profiles, the position of the wet front): ONE streaming pass over the live records in their current order that
+ * bins the selected particles into the columns of a 2-D map.  The columns run along `axis`; the map spans the two other
+ * axes ja < jb, n[0] columns along ja times n[1] along jb, column (k_a, k_b) at index k_a * n[1] + k_b.
+ * The call READS x, v and the flags (32 bytes per particle) and writes NOTHING of the particle state -- it does not even
+ * fold density and pressure back out of a fused step's record, as the diagnostics do: a run with map calls between its
+ * steps ends bit-identical to the run without.
+ * SELECTED: a particle whose material is fluid and, unless object_id < 0, whose object id equals object_id.
+ * ARITHMETIC per selected particle, f32, operation by operation, nothing contracted into an fma, no reciprocal, no divide:
+ *     f_j = floorf((x_j - origin_j) * inv_cell_j)      for j = ja, jb: one subtract, one multiply, floorf
+ *     k_j = (int)f_j; the particle is OUTSIDE unless 0 <= f_j < n_j for both j (a NaN is outside): it is counted in
+ *     `outside` and binned nowhere.  Otherwise its column receives
+ *     count    += 1                                                         (i64)
+ *     sum_v[a] += llrint((double)fmaxf(fminf(v_a, 65536.f), -65536.f) * 2^20)   a = 0, 1, 2  (i64; round to nearest even)
+ *     top       = max(top, x[axis]),  bottom = min(bottom, x[axis])         (f32)
+ * inv_cell is computed by the caller (the Python layer: f32(1) / f32(cell)) and passed by value.  Each velocity term is
+ * bounded by 2^36, so the i64 sums hold 2^26 particles in one column.
+ * DETERMINISTIC: every accumulation is an integer sum or an extremum (which travels as the order-preserving u32 image of
+ * the f32 bits, so negative coordinates and signed zeros order one way only); the map is the same bits for any particle
+ * order and any scheduling.  There is no floating-point atomic.  csrc/sph_columns.hip describes the on-chip combining.
+ * An empty column has count 0, sums 0 and top = bottom = 0 (as the bounds of an empty SphDiagRow).
+ * sph_columns_reduce enqueues three launches (clear, scatter, finish) on the context's stream; sph_columns_download copies
+ * the map of the LAST reduce (count [n0 * n1], sum_v [3][n0 * n1], top, bottom [n0 * n1]; any pointer may be NULL) and
+ * synchronises.  The map's buffers are allocated by the first reduce, again when n[0] * n[1] changes, and freed with the
+ * context.
+ * SPH_E_INVALID: axis outside 0..2, n[j] < 1, n[0] * n[1] > SPH_COLUMNS_MAX, an inv_cell that is not finite and positive, a
+ * non-finite origin; for the download n_columns != n[0] * n[1] of the last reduce.  SPH_E_STATE: download before any
+ * reduce; single-domain contexts only: a slab rank, whose ghost records would be counted twice, answers SPH_E_STATE.
+ * ==================================================================================== */
+#define SPH_COLUMNS_MAX (1 << 20)
+#define SPH_COLUMNS_V_SCALE_LOG2 20
+typedef struct SphColumnParams {
+    int32_t axis;          /* 0, 1, 2: the axis the columns run along */
+    int32_t n[2];          /* columns along the two other axes, ascending axis order; n[0] * n[1] <= SPH_COLUMNS_MAX */
+    float origin[2], inv_cell[2];
+    int32_t object_id;     /* -1: every fluid particle */
+} SphColumnParams;
+typedef struct SphColumnTotals { int64_t selected, binned, outside; } SphColumnTotals;
+int32_t sph_columns_reduce(SphContext* ctx, const SphColumnParams* params);   /* enqueues */
+int32_t sph_columns_download(SphContext* ctx, int64_t* count, int64_t* sum_v /* [3][n0*n1] */, float* top, float* bottom,
+                             int32_t n_columns, SphColumnTotals* totals);   /* any pointer may be NULL; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

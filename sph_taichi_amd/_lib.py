@@ -89,6 +89,20 @@ class SphDiagRow(C.Structure):
 # launch shape of the diagnostics reduction (SPH_DIAG_BLOCKS x SPH_DIAG_THREADS, striding) and its object limit
 DIAG_BLOCKS, DIAG_THREADS, DIAG_MAX_OBJECTS = 1024, 256, 96
 
+class SphColumnParams(C.Structure):
+    """Mirror of `struct SphColumnParams` (include/sph_hip.h)."""
+    _fields_ = [("axis", C.c_int32), ("n", C.c_int32 * 2), ("origin", C.c_float * 2), ("inv_cell", C.c_float * 2),
+                ("object_id", C.c_int32)]
+
+
+class SphColumnTotals(C.Structure):
+    """Mirror of `struct SphColumnTotals` (include/sph_hip.h)."""
+    _fields_ = [("selected", C.c_int64), ("binned", C.c_int64), ("outside", C.c_int64)]
+
+
+# limits of the column maps: columns per map, and the fixed-point scale 2^20 of the velocity sums
+COLUMNS_MAX, COLUMNS_V_SCALE_LOG2 = 1 << 20, 20
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -200,6 +214,9 @@ SYMBOLS = [
     ("sph_set_time", C.c_int32, [_ctx, C.c_double]),
     ("sph_diag_reduce", C.c_int32, [_ctx]),
     ("sph_diag_download", C.c_int32, [_ctx, C.POINTER(SphDiagRow), C.c_int32]),
+    ("sph_columns_reduce", C.c_int32, [_ctx, C.POINTER(SphColumnParams)]),
+    ("sph_columns_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.POINTER(SphColumnTotals)]),
 ]
 
 _LIB = None

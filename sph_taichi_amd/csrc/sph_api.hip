@@ -419,6 +419,7 @@ int32_t sph_destroy(SphContext* c) {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     sph_render_release(c);
     sph_diag_release(c);
+    sph_columns_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);

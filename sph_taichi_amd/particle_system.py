@@ -413,6 +413,16 @@ class ParticleSystem:
         from . import diagnostics as _diag
         return _diag.reduce(self)
 
+    def column_map(self, axis=1, cell=None, origin=None, shape=None, object_id=None):
+        """Depth-integrated map of the fluid over the two axes other than `axis` (columns.ColumnMap): per column the
+        particle count, top and bottom of the fluid and the summed velocity; `depth`, `surface`, `velocity`, `gauge(points)`
+        and `wet_extent()` follow from them.  `cell` (one number or one per horizontal axis) defaults to the support radius,
+        `origin` to 0, `shape` to ceil(domain_size_j / cell); `object_id` restricts the map to one fluid object.  One
+        streaming pass on the device behind whatever was enqueued; only the map is copied back (synchronises).  Reads x, v
+        and the flags; changes nothing a later step reads."""
+        from . import columns as _columns
+        return _columns.reduce(self, axis=axis, cell=cell, origin=origin, shape=shape, object_id=object_id)
+
     def build_time_step_controller(self, solver):
         """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""
         from . import timestep as _timestep

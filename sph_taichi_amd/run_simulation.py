@@ -15,6 +15,12 @@ per-phase HIP-event breakdown (sort / neighbour / force / integrate).
 A scene whose Configuration holds an "adaptiveTimeStep" object gets its dt from the CFL criteria of timestep.py, once per
 frame (one reduction on the device and one host synchronisation; dt never changes inside a frame's steps).
 `--diagnostics PATH` writes one JSON line per exported interval: frame, time, dt and the all-particle diagnostics row.
+`--gauges PATH` writes one JSON line per exported interval from a column map of the fluid (columns.py): frame, time, the wet
+extent (the front), selected / outside counts and, if the scene's Configuration holds
+"gauges": {"axis": 1, "cell": c, "points": [[a, b], ...]}, depth / surface / velocity at those points; without the key the
+defaults apply and no point rows are written.  `--heightmap_dir DIR` writes the map's surface elevation as an 8-bit grey PNG
+per interval, scaled by the domain's extent along the map's axis.  Both are independent of `exportFrame` and `--diagnostics`;
+with neither given no map is made.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -51,6 +57,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--load_state", default="", help="continue from a checkpoint written by --save_state")
     ap.add_argument("--diagnostics", default="", metavar="PATH",
                     help="write one JSON line per exported interval here: frame, time, dt, the all-particle diagnostics row")
+    ap.add_argument("--gauges", default="", metavar="PATH",
+                    help="write one JSON line per exported interval here: frame, time, wet extent, selected / outside, and the "
+                         "scene's gauge points read off a column map")
+    ap.add_argument("--heightmap_dir", default="", metavar="DIR",
+                    help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
                     help="size of the exportFrame images (the reference's window is 1024 x 1024)")
     ap.add_argument("--camera", type=float, nargs=6, default=None, metavar=("EX", "EY", "EZ", "LX", "LY", "LZ"),
@@ -93,6 +104,14 @@ def main(argv=None):
         ps.set_option(_lib.OPT_TIMING, 1)
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
+    gauges = gauges_out = None
+    if args.gauges or args.heightmap_dir:
+        from . import columns as _columns
+        from .render import write_png as write_heightmap
+        gauges = _columns.gauges_config(config)
+        gauges_out = open(args.gauges, "w") if args.gauges else None
+        if args.heightmap_dir:
+            os.makedirs(args.heightmap_dir, exist_ok=True)
 
     cnt = cnt_ply = frames_written = 0
     render_s = 0.0
@@ -104,6 +123,18 @@ def main(argv=None):
             diag = diag if diag is not None else ps.diagnostics()
             diag_out.write(json.dumps({"frame": cnt, "time": diag.time, "dt": float(np.float32(solver.dt[None])),
                                        "total": diag.total.as_dict()}) + "\n")
+        if gauges is not None and cnt % output_interval == 0:
+            cmap = ps.column_map(axis=gauges["axis"], cell=gauges["cell"])
+            if gauges_out is not None:
+                ext = cmap.wet_extent()
+                row = {"frame": cnt, "time": cmap.time, "wet_extent": [list(e) for e in ext] if ext is not None else None,
+                       "selected": cmap.selected, "outside": cmap.outside}
+                if gauges["points"]:
+                    row["gauges"] = _columns.gauge_rows(cmap, gauges["points"])
+                gauges_out.write(json.dumps(row) + "\n")
+            if args.heightmap_dir:
+                write_heightmap(os.path.join(args.heightmap_dir, f"{cnt:06}.png"),
+                                _columns.heightmap_image(cmap, float(ps.domain_size[cmap.axis])))
         if output_frames and cnt % output_interval == 0:
             ps.sync()                          # the frame's cost, not the steps still in flight before it
             tr = time.perf_counter()
@@ -135,6 +166,8 @@ def main(argv=None):
         report["dt_min_used"], report["dt_max_used"] = controller.dt_min_used, controller.dt_max_used
     if diag_out is not None:
         diag_out.close()
+    if gauges_out is not None:
+        gauges_out.close()
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
