@@ -615,6 +615,59 @@ int32_t sph_columns_reduce(SphContext* ctx, const SphColumnParams* params);   /*
 int32_t sph_columns_download(SphContext* ctx, int64_t* count, int64_t* sum_v /* [3][n0*n1] */, float* top, float* bottom,
                              int32_t n_columns, SphColumnTotals* totals);   /* any pointer may be NULL; synchronises */
 
+/* ======================================================================================
+ * Particle export (the reference's exportPly path, run_simulation.py:101-107 + ParticleSystem.dump, particle_system.py:409-418,
+ * downloads object_id, x and v of ALL particles, masks them on the host and writes text, in the cell-sorted order of the moment):
+ * a device-side SELECTION of the live records, ORDERED BY PERSISTENT ID and packed on the device into the exact byte rows of a
+ * binary PLY vertex body; the host writes a header and one contiguous buffer, and vertex k is the same particle in every file.
+ * SELECTED: a record whose material equals `material` (unless -1), whose object id is in object_ids[0..n_objects) (unless n_objects
+ * is 0), whose persistent id satisfies pid % pid_stride == pid_phase (a decimation that keeps the SAME particles in every frame)
+ * and, if use_box, whose position satisfies box_lo[a] <= x[a] <= box_hi[a] on all three axes, compared as f32 (a NaN is outside).
+ * ROW: the chosen fields in the order of the SPH_EXPORT_* bits, 4 bytes per word, no padding: x y z [vx vy vz] [density] [pressure]
+ * [mass] [id] [object]; row_bytes = 4 * words.  ORDER: row r belongs to the selected particle with the r-th smallest persistent id.
+ * VALUES: the bits sph_download would return for those fields at that moment; when density or pressure is requested, what a fused
+ * step left in its own record is materialised first (as any download of them does), otherwise not.  The kernels do NO arithmetic on
+ * a value: the only computations are the box comparison and pid % pid_stride.
+ * The call READS xm / vf / aux and writes nothing of the particle state: a run with export calls between its steps ends bit-identical
+ * to the run without.  DETERMINISTIC by construction: the output is a function of the SET of selected records, never of their order
+ * in memory or of scheduling (csrc/sph_export.hip: a compaction through a table indexed by the id; no kernel waits for another
+ * workgroup).
+ * DUPLICATE IDS: unique persistent ids below cold_capacity are an invariant of the context (x_0 and color are keyed by them).  If the
+ * number of DISTINCT ids marked differs from the number of records selected, duplicate_ids is their difference and
+ * sph_export_download answers SPH_E_STATE with a message; no row order is defined then.
+ * sph_export_select enqueues five launches (clear, mark, tile counts, tile offsets, pack) on the context's stream; sph_export_info
+ * returns the counts of the LAST select and synchronises; sph_export_download copies its rows (bytes == rows * row_bytes) and
+ * synchronises.  Buffers: an i32 slot table of cold_capacity entries (rounded up to whole tiles), the tile counts and offsets, and a
+ * row buffer for the live count times row_bytes; allocated by the first select, the row buffer again when a later select needs
+ * more, freed with the context.  A context that never exports allocates nothing.
+ * SPH_E_INVALID: fields without SPH_EXPORT_X or with unknown bits, n_objects outside [0, SPH_EXPORT_MAX_OBJECTS], pid_stride < 1,
+ * pid_phase outside [0, pid_stride), with use_box a non-finite bound or box_lo > box_hi; for the download a `bytes` that does not
+ * match.  SPH_E_STATE: info or download before any select; single-domain contexts only: a slab rank, whose ghost records would be
+ * exported twice, answers SPH_E_STATE.
+ * ==================================================================================== */
+#define SPH_EXPORT_X        1   /* f32 x 3  (always required)            */
+#define SPH_EXPORT_V        2   /* f32 x 3                                */
+#define SPH_EXPORT_DENSITY  4   /* f32                                    */
+#define SPH_EXPORT_PRESSURE 8   /* f32                                    */
+#define SPH_EXPORT_MASS     16  /* f32  (SPH_F_M)                         */
+#define SPH_EXPORT_ID       32  /* i32  persistent id                     */
+#define SPH_EXPORT_OBJECT   64  /* i32  object id                         */
+#define SPH_EXPORT_MAX_OBJECTS 32
+typedef struct SphExportParams {
+    int32_t fields;                 /* mask of the above; row = the chosen fields in THIS order, 4 bytes per word, no padding */
+    int32_t material;               /* -1: any; else == the particle's SPH_F_MATERIAL */
+    int32_t n_objects;              /* 0: every object; else the particle's object id must be in object_ids[0..n) */
+    int32_t object_ids[SPH_EXPORT_MAX_OBJECTS];
+    int32_t pid_stride, pid_phase;  /* keep pid % pid_stride == pid_phase (stride >= 1, 0 <= phase < stride): a decimation that keeps
+                                       the SAME particles in every frame */
+    int32_t use_box;                /* != 0: keep lo[a] <= x[a] <= hi[a] for a = 0, 1, 2, compared as f32 (a NaN is outside) */
+    float box_lo[3], box_hi[3];
+} SphExportParams;
+typedef struct SphExportInfo { int64_t selected, rows; int32_t row_bytes, duplicate_ids; } SphExportInfo;
+int32_t sph_export_select(SphContext* ctx, const SphExportParams* params);   /* enqueues on the context's stream */
+int32_t sph_export_info(SphContext* ctx, SphExportInfo* info);               /* of the last select; synchronises */
+int32_t sph_export_download(SphContext* ctx, void* host, size_t bytes);      /* bytes == rows * row_bytes; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

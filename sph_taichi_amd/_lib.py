@@ -103,6 +103,21 @@ class SphColumnTotals(C.Structure):
 # limits of the column maps: columns per map, and the fixed-point scale 2^20 of the velocity sums
 COLUMNS_MAX, COLUMNS_V_SCALE_LOG2 = 1 << 20, 20
 
+class SphExportParams(C.Structure):
+    """Mirror of `struct SphExportParams` (include/sph_hip.h)."""
+    _fields_ = [("fields", C.c_int32), ("material", C.c_int32), ("n_objects", C.c_int32), ("object_ids", C.c_int32 * 32),
+                ("pid_stride", C.c_int32), ("pid_phase", C.c_int32), ("use_box", C.c_int32), ("box_lo", _F3), ("box_hi", _F3)]
+
+
+class SphExportInfo(C.Structure):
+    """Mirror of `struct SphExportInfo` (include/sph_hip.h)."""
+    _fields_ = [("selected", C.c_int64), ("rows", C.c_int64), ("row_bytes", C.c_int32), ("duplicate_ids", C.c_int32)]
+
+
+# field bits of the particle export (SPH_EXPORT_*) and its object-list limit
+EXPORT_X, EXPORT_V, EXPORT_DENSITY, EXPORT_PRESSURE, EXPORT_MASS, EXPORT_ID, EXPORT_OBJECT = 1, 2, 4, 8, 16, 32, 64
+EXPORT_MAX_OBJECTS = 32
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -217,6 +232,9 @@ SYMBOLS = [
     ("sph_columns_reduce", C.c_int32, [_ctx, C.POINTER(SphColumnParams)]),
     ("sph_columns_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.POINTER(SphColumnTotals)]),
+    ("sph_export_select", C.c_int32, [_ctx, C.POINTER(SphExportParams)]),
+    ("sph_export_info", C.c_int32, [_ctx, C.POINTER(SphExportInfo)]),
+    ("sph_export_download", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
 ]
 
 _LIB = None

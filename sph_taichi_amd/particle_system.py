@@ -423,6 +423,17 @@ class ParticleSystem:
         from . import columns as _columns
         return _columns.reduce(self, axis=axis, cell=cell, origin=origin, shape=shape, object_id=object_id)
 
+    def export_particles(self, objects=None, material=None, fields=("velocity",), box=None, every=1, phase=0):
+        """The selected particles ORDERED BY PERSISTENT ID, packed on the device into the rows of a binary PLY vertex body
+        (export.ParticleExport: `.data` is a structured array x y z [vx vy vz] [density] [pressure] [mass] [id] [object],
+        `.write_ply(path)` writes it).  `objects`: ids to keep (None: all); `material`: "fluid", "solid" or an id (None: any);
+        `fields`: names from velocity, density, pressure, mass, id, object (the position is always there); `box` = (lo, hi):
+        keep lo <= x <= hi; `every`, `phase`: keep pid % every == phase, the same particles in every call.  Row k is the
+        same particle in every export of one selection.  One pass on the device behind whatever was enqueued; only the rows
+        are copied back (synchronises).  Reads the records; changes nothing a later step reads."""
+        from . import export as _export
+        return _export.export(self, objects=objects, material=material, fields=fields, box=box, every=every, phase=phase)
+
     def build_time_step_controller(self, solver):
         """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""
         from . import timestep as _timestep

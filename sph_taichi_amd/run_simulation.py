@@ -21,6 +21,10 @@ extent (the front), selected / outside counts and, if the scene's Configuration 
 defaults apply and no point rows are written.  `--heightmap_dir DIR` writes the map's surface elevation as an 8-bit grey PNG
 per interval, scaled by the domain's extent along the map's axis.  Both are independent of `exportFrame` and `--diagnostics`;
 with neither given no map is made.
+A scene whose Configuration holds "exportParticles": {"objects": [0], "material": "fluid", "fields": ["velocity", "id"],
+"box": [[lo], [hi]], "every": 1, "phase": 0} (every key optional; {} = every particle, positions only) writes
+`{scene}_output/particles_{cnt_ply:06}.ply` per interval: a binary PLY whose vertices are selected, ordered by persistent id and
+packed on the device (export.py), so vertex k is the same particle in every file.  `exportPly` is untouched.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -83,7 +87,9 @@ def main(argv=None):
     series_prefix = "{}_output/particle_object_{}.ply".format(scene_name, "{}")
     if output_frames:
         os.makedirs(f"{scene_name}_output_img", exist_ok=True)
-    if output_ply or output_obj:
+    from . import export as _export
+    export_spec = _export.export_config(config)        # "exportParticles": None when the key is absent
+    if output_ply or output_obj or export_spec is not None:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = None
@@ -113,8 +119,8 @@ def main(argv=None):
         if args.heightmap_dir:
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
-    cnt = cnt_ply = frames_written = 0
-    render_s = 0.0
+    cnt = cnt_ply = frames_written = particle_files = 0
+    render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
         solver.step(substeps)
@@ -147,6 +153,13 @@ def main(argv=None):
                 obj_id = 0
                 np_pos = ps.dump(obj_id=obj_id)["position"]
                 write_ply_ascii(series_prefix.format(0).replace(".ply", f"_{cnt_ply:06}.ply"), np_pos)
+            if export_spec is not None:
+                ps.sync()                      # the file's cost, not the steps still in flight before it
+                te = time.perf_counter()
+                ps.export_particles(**export_spec).write_ply(f"{scene_name}_output/particles_{cnt_ply:06}.ply",
+                                                             comments=(f"frame {cnt}",))
+                export_s += time.perf_counter() - te
+                particle_files += 1
             if output_obj:
                 ps.update_kinematic_meshes()       # kinematic bodies ("motion"): the mesh at the current pose
                 for r_body_id in ps.object_id_rigid_body:
@@ -171,6 +184,9 @@ def main(argv=None):
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
+    if particle_files:
+        report["particle_files_written"] = particle_files
+        report["export_ms_per_file"] = round(export_s / particle_files * 1e3, 4)
     if args.timing:
         tm = _lib.SphTimings()
         ps._call("sph_get_timings", tm)
