@@ -668,6 +668,53 @@ int32_t sph_export_select(SphContext* ctx, const SphExportParams* params);   /* 
 int32_t sph_export_info(SphContext* ctx, SphExportInfo* info);               /* of the last select; synchronises */
 int32_t sph_export_download(SphContext* ctx, void* host, size_t bytes);      /* bytes == rows * row_bytes; synchronises */
 
+/* ======================================================================================
+ * Surface frames (no reference counterpart: its window draws every particle as a sphere): a SECOND frame style beside the
+ * sphere frame above, which it leaves untouched.  The fluid is drawn as one screen-space surface -- per pixel the nearest
+ * fluid depth and the summed fluid thickness are splatted, the depth is smoothed in image space by a compactly supported
+ * bilateral (biweight) filter whose pixel radius follows the depth, normals are taken from the smoothed depth, and the
+ * surface is shaded (diffuse + Blinn-Phong + Schlick Fresnel) with absorption by thickness over the OPAQUE layer: the
+ * sphere frame's own picture of every particle that is not fluid plus the box edges.
+ * Camera, image size, particle radius, box and invisible objects are those of the last sph_render_set_params /
+ * sph_render_set_invisible; a surface frame before them answers SPH_E_STATE, and so does one before sph_surface_set_params.
+ * Passes per frame, all enqueued on the context's stream (csrc/sph_surface.hip states the arithmetic operation by operation
+ * and lists the bytes): clear; opaque splat; fluid splat; `iterations` depth-smoothing passes; one thickness-smoothing pass;
+ * shade and resolve.  A frame READS xm, vf (flags), the pid and the colours and writes NOTHING of the particle state; density
+ * and pressure are not needed and are not folded out of a fused step's record.  The only accumulations are a 64-bit integer
+ * minimum, a 32-bit integer minimum and a 32-bit integer sum; every later pass computes one pixel from a fixed window in a fixed
+ * order: the three outputs are functions of the SET of particles, bit for bit, whatever their order or the scheduling.
+ * The buffers (39 bytes per pixel) are allocated by the first surface frame, again when the size changes, and freed with the
+ * context; a context that never asks for a surface frame allocates nothing.
+ * SPH_E_INVALID (sph_surface_set_params; the last good parameters stay in force): iterations outside [0, 8], filter_radius or
+ * depth_range not positive and finite, a fluid_color / sky component outside [0, 1], a negative or non-finite absorb component,
+ * f0 outside [0, 1], specular negative or non-finite; for a download a `bytes` that does not match the last frame.
+ * SPH_E_STATE: a frame before the parameters, a download before any frame; single-domain contexts only: a slab rank answers
+ * SPH_E_STATE, as for the sphere frame.
+ * ==================================================================================== */
+#define SPH_SURFACE_MAX_FILTER_R 16   /* the filter window never exceeds (2 * 16 + 1)^2 pixels */
+#define SPH_SURFACE_MAX_ITERATIONS 8
+#define SPH_SURFACE_PASSES 6          /* clear, opaque splat, fluid splat, depth smoothing (all iterations), thickness smoothing, shade */
+typedef struct SphSurfaceParams {
+    int32_t iterations;        /* depth-smoothing passes, 0..SPH_SURFACE_MAX_ITERATIONS */
+    float filter_radius;       /* world units: the filter's pixel radius at depth z is ceil(filter_radius * focal / z), at most 16 */
+    float depth_range;         /* world units: a neighbour whose depth differs by this much or more has weight 0 */
+    float fluid_color[3];      /* in [0, 1] */
+    float absorb[3];           /* >= 0, per world unit: transmittance 1 / (1 + absorb * thickness)^2 */
+    float sky[3];              /* in [0, 1]: what the Fresnel term reflects */
+    float f0;                  /* in [0, 1]: reflectance at normal incidence (water: 0.02) */
+    float specular;            /* >= 0: weight of the (n.h)^64 highlight */
+} SphSurfaceParams;
+int32_t sph_surface_set_params(SphContext* ctx, const SphSurfaceParams* params);
+int32_t sph_surface_frame(SphContext* ctx);                                   /* enqueues */
+int32_t sph_surface_download(SphContext* ctx, uint8_t* rgb, size_t bytes);    /* u8 [height, width, 3], row 0 at the top; synchronises */
+/* f32 [height, width]: the smoothed fluid depth where the fluid is shown, else the opaque layer's depth, +inf where nothing is */
+int32_t sph_surface_download_depth(SphContext* ctx, float* depth, size_t bytes);
+/* f32 [height, width]: smoothed fluid thickness in front of the opaque layer, world units; 0 where no fluid is shown */
+int32_t sph_surface_download_thickness(SphContext* ctx, float* thickness, size_t bytes);
+/* A measuring aid: one surface frame with a HIP event between its passes; ms[k] = device time of pass k in the order of
+ * SPH_SURFACE_PASSES (n must equal it).  Synchronises; the frame it leaves is an ordinary one. */
+int32_t sph_surface_frame_timed(SphContext* ctx, float* ms, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

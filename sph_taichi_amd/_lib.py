@@ -118,6 +118,16 @@ class SphExportInfo(C.Structure):
 EXPORT_X, EXPORT_V, EXPORT_DENSITY, EXPORT_PRESSURE, EXPORT_MASS, EXPORT_ID, EXPORT_OBJECT = 1, 2, 4, 8, 16, 32, 64
 EXPORT_MAX_OBJECTS = 32
 
+class SphSurfaceParams(C.Structure):
+    """Mirror of `struct SphSurfaceParams` (include/sph_hip.h)."""
+    _fields_ = [("iterations", C.c_int32), ("filter_radius", C.c_float), ("depth_range", C.c_float), ("fluid_color", _F3),
+                ("absorb", _F3), ("sky", _F3), ("f0", C.c_float), ("specular", C.c_float)]
+
+
+# limits of the surface frame (SPH_SURFACE_*) and the number of passes sph_surface_frame_timed reports
+SURFACE_MAX_FILTER_R, SURFACE_MAX_ITERATIONS, SURFACE_PASSES = 16, 8, 6
+SURFACE_PASS_NAMES = ("clear", "opaque_splat", "fluid_splat", "depth_smoothing", "thickness_smoothing", "shade_resolve")
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -235,6 +245,12 @@ SYMBOLS = [
     ("sph_export_select", C.c_int32, [_ctx, C.POINTER(SphExportParams)]),
     ("sph_export_info", C.c_int32, [_ctx, C.POINTER(SphExportInfo)]),
     ("sph_export_download", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_surface_set_params", C.c_int32, [_ctx, C.POINTER(SphSurfaceParams)]),
+    ("sph_surface_frame", C.c_int32, [_ctx]),
+    ("sph_surface_download", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_surface_download_depth", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_surface_download_thickness", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_surface_frame_timed", C.c_int32, [_ctx, C.POINTER(C.c_float), C.c_int32]),
 ]
 
 _LIB = None

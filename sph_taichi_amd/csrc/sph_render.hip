@@ -61,133 +61,15 @@
 #include <math.h>
 #include <new>
 
-#include "sph_internal.h"
+#include "sph_render_dev.h"   // RenderCam, SphRender, the sprite / fragment / box-edge device functions (shared with sph_surface.hip)
 
 #pragma clang fp contract(off)
-
-#define SPH_RENDER_SMALL_R 4.0f    // sprites up to this pixel radius (at most 9 x 9 pixels) are rasterised by one lane
-#define SPH_RENDER_MAX_R 512.0f    // larger sprites are cropped to the square of this half-width around their centre
-#define SPH_RENDER_MAX_DIM 16384
-#define RTPB 256
-
-struct RenderCam {
-    int W, H, S;              // image size; samples per box edge
-    int n_invisible;
-    int invisible[SPH_RENDER_MAX_INVISIBLE];
-    float ex, ey, ez;
-    float rx, ry, rz, ux, uy, uz, fx, fy, fz;
-    float focal, cx, cy, radius, r2, fr, near_plane;
-    float Lx, Ly, Lz, ambient;
-    float bex, bey, bez;      // box_end
-    unsigned box_rgb, background;
-    int draw_box;
-};
-
-struct SphRender {
-    SphRenderParams p;
-    RenderCam cam;
-    int W, H;                              // what the buffers below are sized for
-    unsigned long long* keys;              // [W * H]
-    unsigned* big_count;                   // device counter of the large-sprite list
-    unsigned char* rgb;                    // [H * W * 3]
-    float* depth;                          // [H * W]
-    bool have_frame;
-};
-
-struct Sprite { float a, b, zc, px, py, inv; int i0, i1, j0, j1; float R; };
-
-__device__ __forceinline__ float rdot(float ax, float ay, float az, float dx, float dy, float dz) { return (ax * dx + ay * dy) + az * dz; }
-
-__device__ __forceinline__ bool render_visible(const RenderCam& cam, int flags) {
-    const int oid = sph_flags_object(flags);
-    for (int k = 0; k < cam.n_invisible; ++k)
-        if (cam.invisible[k] == oid) return false;
-    return true;
-}
-
-// projection and clamped bounding box of one particle; false = culled
-__device__ __forceinline__ bool render_sprite(const RenderCam& cam, float x, float y, float z, Sprite& s) {
-    const float dx = x - cam.ex, dy = y - cam.ey, dz = z - cam.ez;
-    s.a = rdot(cam.rx, cam.ry, cam.rz, dx, dy, dz);
-    s.b = rdot(cam.ux, cam.uy, cam.uz, dx, dy, dz);
-    s.zc = rdot(cam.fx, cam.fy, cam.fz, dx, dy, dz);
-    if (!(s.zc >= cam.near_plane)) return false;
-    s.px = cam.cx + (cam.focal * s.a) / s.zc;
-    s.py = cam.cy - (cam.focal * s.b) / s.zc;
-    s.R = cam.fr / s.zc;
-    s.inv = s.zc / cam.focal;
-    if (!(isfinite(s.px) && isfinite(s.py) && isfinite(s.R))) return false;
-    const float Rb = fminf(s.R, SPH_RENDER_MAX_R);
-    // clamped in float first: the conversions below see values in [-1, 16384] (a sprite beside the image: an empty range)
-    s.i0 = (int)fminf(fmaxf(ceilf((s.px - Rb) - 0.5f), 0.0f), (float)cam.W);
-    s.i1 = (int)fmaxf(fminf(floorf((s.px + Rb) - 0.5f), (float)(cam.W - 1)), -1.0f);
-    s.j0 = (int)fminf(fmaxf(ceilf((s.py - Rb) - 0.5f), 0.0f), (float)cam.H);
-    s.j1 = (int)fmaxf(fminf(floorf((s.py + Rb) - 0.5f), (float)(cam.H - 1)), -1.0f);
-    return s.i0 <= s.i1 && s.j0 <= s.j1;
-}
-
-__device__ __forceinline__ void render_fragment(const RenderCam& cam, unsigned long long* __restrict__ keys, const Sprite& s,
-                                                const float kc[3], int i, int j) {
-    const float dx = (((float)i + 0.5f) - s.px) * s.inv;
-    const float dy = (s.py - ((float)j + 0.5f)) * s.inv;
-    const float h2 = (cam.r2 - dx * dx) - dy * dy;
-    if (!(h2 >= 0.0f)) return;
-    const float hh = sqrtf(h2);
-    const float z = s.zc - hh;
-    if (!(z > 0.0f)) return;
-    const float nx = dx / cam.radius, ny = dy / cam.radius, nz = hh / cam.radius;
-    const float lx = cam.Lx - (s.a + dx), ly = cam.Ly - (s.b + dy), lz = z - cam.Lz;
-    const float ll = sqrtf((lx * lx + ly * ly) + lz * lz);
-    const float nl = ll > 0.0f ? ((nx * lx + ny * ly) + nz * lz) / ll : 0.0f;
-    const float shade = cam.ambient + (1.0f - cam.ambient) * fmaxf(nl, 0.0f);
-    unsigned rgb = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float t = fminf(fmaxf(kc[k] * shade, 0.0f), 1.0f);
-        rgb = (rgb << 8) | (unsigned)(t * 255.0f + 0.5f);
-    }
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | rgb;
-    unsigned long long* p = keys + (size_t)j * cam.W + i;      // 0 <= i < W, 0 <= j < H by the clamped box
-    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-}
-
-__device__ __forceinline__ void render_colour(const int* __restrict__ color_cold, int pid, int cold_cap, float kc[3]) {
-    const bool ok = pid >= 0 && pid < cold_cap;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) kc[k] = ok ? (float)color_cold[3 * (size_t)pid + k] / 255.0f : 0.0f;
-}
 
 __global__ __launch_bounds__(RTPB) void k_render_clear(unsigned long long* __restrict__ keys, int n_pix, unsigned background,
                                                        unsigned* __restrict__ big_count) {
     const int i = blockIdx.x * RTPB + threadIdx.x;
     if (i == 0) *big_count = 0u;
     if (i < n_pix) keys[i] = 0xFFFFFFFF00000000ull | background;
-}
-
-__device__ __forceinline__ void render_box_sample(const RenderCam& cam, unsigned long long* __restrict__ keys, int t) {
-    if (t >= 12 * cam.S) return;
-    const int e = t / cam.S, m = t - e * cam.S;
-    // edge e: axis e / 4, the four edges along it told apart by the two other coordinates (0 or box_end)
-    const int axis = e >> 2, c1 = e & 1, c2 = (e >> 1) & 1;
-    const float end[3] = {cam.bex, cam.bey, cam.bez};
-    float A[3], B[3];
-    const int o1 = (axis + 1) % 3, o2 = (axis + 2) % 3;
-    A[axis] = 0.0f; B[axis] = end[axis];
-    A[o1] = B[o1] = c1 ? end[o1] : 0.0f;
-    A[o2] = B[o2] = c2 ? end[o2] : 0.0f;
-    const float tt = ((float)m + 0.5f) / (float)cam.S;
-    const float dx = (A[0] + (B[0] - A[0]) * tt) - cam.ex, dy = (A[1] + (B[1] - A[1]) * tt) - cam.ey, dz = (A[2] + (B[2] - A[2]) * tt) - cam.ez;
-    const float a = rdot(cam.rx, cam.ry, cam.rz, dx, dy, dz);
-    const float b = rdot(cam.ux, cam.uy, cam.uz, dx, dy, dz);
-    const float zc = rdot(cam.fx, cam.fy, cam.fz, dx, dy, dz);
-    if (!(zc >= cam.near_plane)) return;
-    const float px = cam.cx + (cam.focal * a) / zc;
-    const float py = cam.cy - (cam.focal * b) / zc;
-    if (!(px >= 0.0f && px < (float)cam.W && py >= 0.0f && py < (float)cam.H)) return;   // (false for NaN too)
-    const int i = (int)px, j = (int)py;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(zc) << 32) | cam.box_rgb;
-    unsigned long long* p = keys + (size_t)j * cam.W + i;
-    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
 }
 
 // blocks [0, particle_blocks): one lane per particle; blocks behind them: one lane per box-edge sample

@@ -508,6 +508,50 @@ class ParticleSystem:
         self._call("sph_render_download_depth", out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
+    # ---- surface frames (csrc/sph_surface.hip; the reference's window has no such style) ----
+    def _first_fluid_colour(self):
+        blocks = self.cfg.get_fluid_blocks()
+        return tuple(blocks[0].get("color", (50, 100, 200))) if blocks else (50, 100, 200)
+
+    def render_surface(self, camera=None, invisible_objects=(), size=(1024, 1024), style=None) -> np.ndarray:
+        """The fluid as ONE shaded surface -- screen-space depth and thickness, the depth smoothed in image space, normals
+        from it, absorption by thickness, Fresnel and a highlight -- over the solids and the domain box drawn as `render`
+        draws them; uint8 [H, W, 3] with row 0 at the top.  `style`: a `render.SurfaceStyle` (None: its defaults, with the
+        filter radius 3 x and the depth range 4 x the particle radius and the first fluid block's colour).  Rendered on the
+        GPU behind whatever was enqueued before; only the image is copied back.  Reads the particles; changes nothing."""
+        from . import render as _render
+        cam = camera if camera is not None else _render.Camera()
+        rp = _render.render_params(cam, size, self.particle_radius, self.domain_end)
+        self._call("sph_render_set_params", C.byref(rp))
+        ids = [int(i) for i in invisible_objects]
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        self._call("sph_render_set_invisible", arr, len(ids))
+        sp = _render.surface_params(_render.resolve_style(style, self.particle_radius, self._first_fluid_colour()))
+        self._call("sph_surface_set_params", C.byref(sp))
+        self._call("sph_surface_frame")
+        self._surface_shape = (int(size[1]), int(size[0]))
+        out = np.empty(self._surface_shape + (3,), dtype=np.uint8)
+        self._call("sph_surface_download", out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def _surface_plane(self, symbol, what):
+        shape = getattr(self, "_surface_shape", None)
+        if shape is None:
+            raise _lib.SphError(f"{what}: no surface frame has been rendered")
+        out = np.empty(shape, dtype=np.float32)
+        self._call(symbol, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def render_surface_depth(self) -> np.ndarray:
+        """float32 [H, W] of the last `render_surface`: the smoothed fluid depth where the fluid is shown, else the depth of
+        the solid or box line behind, +inf where nothing was drawn."""
+        return self._surface_plane("sph_surface_download_depth", "render_surface_depth")
+
+    def render_surface_thickness(self) -> np.ndarray:
+        """float32 [H, W] of the last `render_surface`: the smoothed thickness of the fluid in front of the solids along
+        each pixel's ray, in world units; 0 where no fluid is shown."""
+        return self._surface_plane("sph_surface_download_thickness", "render_surface_thickness")
+
     def copy_to_vis_buffer(self, invisible_objects=[]):
         """particle_system.py:392-407 (host copy; there is no GGUI here)."""
         assert self.GGUI

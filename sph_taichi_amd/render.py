@@ -2,6 +2,8 @@
 device renderer uses (csrc/sph_render.hip states the arithmetic), and a PNG writer on zlib + struct.
 
 The picture itself is made on the GPU (`ParticleSystem.render`); nothing here touches particle data.
+`SurfaceStyle` holds the knobs of the second frame style, `ParticleSystem.render_surface` (csrc/sph_surface.hip): the fluid as one
+shaded screen-space surface over the solids.
 """
 from __future__ import annotations
 
@@ -70,6 +72,60 @@ def render_params(camera: Camera, size, radius: float, box_end) -> "_lib.SphRend
     p.ambient = float(camera.ambient)
     p.background = (_lib.C.c_uint8 * 3)(*[int(v) for v in camera.background])
     p.draw_box = 1 if camera.draw_box else 0
+    return p
+
+
+@dataclass
+class SurfaceStyle:
+    """How `ParticleSystem.render_surface` draws the fluid (csrc/sph_surface.hip states the arithmetic).  `None` fields are
+    filled in by the ParticleSystem: filter_radius = 3 x particle radius, depth_range = 4 x particle radius (world units),
+    fluid_color = the first fluid block's colour / 255."""
+    iterations: int = 3                       # depth-smoothing passes, 0..8
+    filter_radius: float | None = None        # world units; in pixels it follows the depth, at most 16
+    depth_range: float | None = None          # world units: depth differences from here on do not mix
+    fluid_color: tuple | None = None          # in [0, 1]
+    absorb: tuple = (18.0, 6.0, 2.0)          # per world unit and channel: transmittance 1 / (1 + absorb * thickness)^2
+    sky: tuple = (0.75, 0.85, 0.95)           # what the Fresnel term reflects
+    f0: float = 0.02                          # reflectance at normal incidence (water)
+    specular: float = 0.6                     # weight of the (n.h)^64 highlight
+
+
+_STYLE_KEYS = {"iterations": "iterations", "filterRadius": "filter_radius", "depthRange": "depth_range", "fluidColor": "fluid_color",
+               "absorb": "absorb", "sky": "sky", "f0": "f0", "specular": "specular"}
+
+
+def surface_style_from_config(entry) -> SurfaceStyle:
+    """The scene file's "surfaceStyle": {...} (camelCase keys of the fields above; colours in [0, 1]); None or {} = defaults."""
+    style = SurfaceStyle()
+    for key, val in (entry or {}).items():
+        if key not in _STYLE_KEYS:
+            raise ValueError(f"surfaceStyle: unknown key {key!r} (known: {', '.join(sorted(_STYLE_KEYS))})")
+        setattr(style, _STYLE_KEYS[key], tuple(val) if isinstance(val, (list, tuple)) else val)
+    return style
+
+
+def resolve_style(style, radius: float, fluid_rgb255) -> SurfaceStyle:
+    """A copy of `style` (None: the defaults) with its None fields filled in for a particle radius and a fluid colour (0..255)."""
+    s = SurfaceStyle(**vars(style)) if style is not None else SurfaceStyle()
+    if s.filter_radius is None:
+        s.filter_radius = 3.0 * float(radius)
+    if s.depth_range is None:
+        s.depth_range = 4.0 * float(radius)
+    if s.fluid_color is None:
+        s.fluid_color = tuple(float(v) / 255.0 for v in fluid_rgb255)
+    return s
+
+
+def surface_params(style: SurfaceStyle) -> "_lib.SphSurfaceParams":
+    """The C struct for a resolved style."""
+    p = _lib.SphSurfaceParams()
+    p.iterations = int(style.iterations)
+    p.filter_radius = float(style.filter_radius)
+    p.depth_range = float(style.depth_range)
+    for name in ("fluid_color", "absorb", "sky"):
+        setattr(p, name, (_lib.C.c_float * 3)(*[float(v) for v in getattr(style, name)]))
+    p.f0 = float(style.f0)
+    p.specular = float(style.specular)
     return p
 
 

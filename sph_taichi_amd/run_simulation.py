@@ -25,6 +25,10 @@ A scene whose Configuration holds "exportParticles": {"objects": [0], "material"
 "box": [[lo], [hi]], "every": 1, "phase": 0} (every key optional; {} = every particle, positions only) writes
 `{scene}_output/particles_{cnt_ply:06}.ply` per interval: a binary PLY whose vertices are selected, ordered by persistent id and
 packed on the device (export.py), so vertex k is the same particle in every file.  `exportPly` is untouched.
+`"frameStyle": "surface"` in the Configuration, or `--frame_style surface`, makes the `exportFrame` images surface frames
+(ParticleSystem.render_surface: the fluid as one shaded surface over the solids) instead of the reference's spheres; an optional
+"surfaceStyle": {"iterations", "filterRadius", "depthRange", "fluidColor", "absorb", "sky", "f0", "specular"} overrides the
+defaults of render.SurfaceStyle.  Absent or "spheres": the frames are what they were.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -70,6 +74,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="size of the exportFrame images (the reference's window is 1024 x 1024)")
     ap.add_argument("--camera", type=float, nargs=6, default=None, metavar=("EX", "EY", "EZ", "LX", "LY", "LZ"),
                     help="camera position and look-at point of the exportFrame images (default: the reference's window camera)")
+    ap.add_argument("--frame_style", choices=["spheres", "surface"], default=None,
+                    help="style of the exportFrame images: every particle a sphere (the reference's window), or the fluid as one "
+                         "shaded surface over the solids (default: the scene's \"frameStyle\", else spheres)")
     return ap
 
 
@@ -92,9 +99,14 @@ def main(argv=None):
     if output_ply or output_obj or export_spec is not None:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
-    camera = None
+    camera = surface_style = None
+    frame_style = args.frame_style or config.get_cfg("frameStyle") or "spheres"
+    if frame_style not in ("spheres", "surface"):
+        raise ValueError(f"frameStyle must be \"spheres\" or \"surface\", not {frame_style!r}")
     if output_frames:
-        from .render import Camera, write_png
+        from .render import Camera, surface_style_from_config, write_png
+        if frame_style == "surface":
+            surface_style = surface_style_from_config(config.get_cfg("surfaceStyle"))
         camera = Camera()
         if args.camera is not None:
             camera.eye, camera.lookat = tuple(args.camera[:3]), tuple(args.camera[3:])
@@ -144,7 +156,11 @@ def main(argv=None):
         if output_frames and cnt % output_interval == 0:
             ps.sync()                          # the frame's cost, not the steps still in flight before it
             tr = time.perf_counter()
-            img = ps.render(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size))
+            if surface_style is not None:
+                img = ps.render_surface(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size),
+                                        style=surface_style)
+            else:
+                img = ps.render(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size))
             render_s += time.perf_counter() - tr
             write_png(f"{scene_name}_output_img/{cnt:06}.png", img)
             frames_written += 1
