@@ -22,8 +22,7 @@
 //            consecutive addresses of each plane.
 // None of this is needed for correctness: unsorted records only make the runs short and the table miss.
 #include <cmath>
-#include <new>
-#include "sph_internal.h"
+#include "sph_observe.h"
 
 #pragma clang fp contract(off)
 
@@ -32,8 +31,6 @@
 #define CT_SLOTS 512
 #define CT_MAX_BLOCKS 1024
 #define CT_V_LIMIT 65536.f
-
-typedef unsigned long long u64;
 
 struct SphColumns {
     // one allocation, planes of `nc` columns each (SoA): count, sum_v[3] (i64), then the three totals, then top, bottom (u32
@@ -56,11 +53,6 @@ __device__ __forceinline__ unsigned f32_to_ordered(float f) {
 }
 __device__ __forceinline__ float ordered_to_f32(unsigned u) {
     return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
-}
-
-__device__ __forceinline__ long long shfl_up_i64(long long v, int off) {
-    const int lo = __shfl_up((int)(v & 0xffffffffll), off, 64), hi = __shfl_up((int)(v >> 32), off, 64);
-    return ((long long)hi << 32) | (unsigned)lo;
 }
 
 struct ColumnTable {
@@ -205,38 +197,17 @@ __global__ __launch_bounds__(CTPB) void k_columns_finish(ColumnPlanes g) {
     if (c == 0) g.totals[1] = g.totals[0] - g.totals[2];
 }
 
-void sph_columns_release(SphContext* c) {
-    if (!c->columns) return;
-    if (c->columns->buf) (void)hipFree(c->columns->buf);
-    delete c->columns;
-    c->columns = nullptr;
-}
+void sph_columns_release(SphContext* c) { sph_observe_release(c->columns, &SphColumns::buf); }
 
 // the state struct, and planes for `nc` columns (allocated again when the map size changes)
 static int columns_state(SphContext* c, int nc) {
-    if (!c->columns) {
-        SphColumns* g = new (std::nothrow) SphColumns();
-        if (!g) return sph_fail(c, SPH_E_NOMEM, "sph_columns_reduce: out of host memory");
-        memset(g, 0, sizeof(*g));
-        c->columns = g;
-    }
-    SphColumns* g = c->columns;
+    SphColumns* g = sph_observe_state(c->columns);
+    if (!g) return sph_fail(c, SPH_E_NOMEM, "sph_columns_reduce: out of host memory");
     if (g->buf && g->nc == nc) return 0;
-    if (g->buf) {
-        SPH_HIP(c, hipStreamSynchronize(c->stream));   // an earlier reduce may still be writing the planes
-        (void)hipFree(g->buf);
-        g->buf = nullptr; g->nc = 0; g->have = false;
-    }
-    const size_t words64 = (size_t)4 * nc + 4, bytes = words64 * 8 + (size_t)2 * nc * 4;
-    void* buf = nullptr;
-    const hipError_t e = hipMalloc(&buf, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        snprintf(c->err, sizeof(c->err), "sph_columns_reduce: hipMalloc of the map's planes (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
-    g->buf = buf;
-    g->count = (long long*)buf;
+    g->nc = 0; g->have = false;
+    const size_t words64 = (size_t)4 * nc + 4;
+    if (int rc = sph_observe_alloc(c, &g->buf, words64 * 8 + (size_t)2 * nc * 4, "sph_columns_reduce", "the map's planes")) return rc;
+    g->count = (long long*)g->buf;
     g->sum_v = g->count + nc;
     g->totals = g->sum_v + (size_t)3 * nc;
     g->top = (unsigned*)(g->totals + 4);
@@ -248,10 +219,8 @@ static int columns_state(SphContext* c, int nc) {
 extern "C" {
 
 int32_t sph_columns_reduce(SphContext* c, const SphColumnParams* p) {
-    if (!c) return SPH_E_INVALID;
-    if (!p) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: params is NULL");
-    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_columns_reduce: this context is a slab rank (its ghost records would be counted twice); "
-                                                         "column maps are reduced on single-domain contexts only");
+    if (c && !p) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: params is NULL");
+    if (int rc = sph_observe_enter(c, "sph_columns_reduce", " (its ghost records would be counted twice); column maps are reduced on single-domain contexts only")) return rc;
     if (p->axis < 0 || p->axis > 2) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: axis must be 0, 1 or 2");
     if (p->n[0] < 1 || p->n[1] < 1) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: n[0] and n[1] must be at least 1");
     if ((long long)p->n[0] * p->n[1] > SPH_COLUMNS_MAX) {
@@ -262,7 +231,6 @@ int32_t sph_columns_reduce(SphContext* c, const SphColumnParams* p) {
         if (!std::isfinite(p->inv_cell[j]) || !(p->inv_cell[j] > 0.f)) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: inv_cell must be finite and positive");
         if (!std::isfinite(p->origin[j])) return sph_fail(c, SPH_E_INVALID, "sph_columns_reduce: origin must be finite");
     }
-    SPH_HIP(c, hipSetDevice(c->device));
     const int nc = p->n[0] * p->n[1];
     if (int rc = columns_state(c, nc)) return rc;
     SphColumns* s = c->columns;
@@ -271,13 +239,10 @@ int32_t sph_columns_reduce(SphContext* c, const SphColumnParams* p) {
     const int map_blocks = (nc + CTPB - 1) / CTPB;
     hipLaunchKernelGGL(k_columns_clear, dim3(map_blocks), dim3(CTPB), 0, c->stream, g);
     SPH_LAUNCH_CHECK(c);
-    const int N = c->N;
-    if (N > 0) {
-        const int tiles = (N + CTPB - 1) / CTPB;
-        const int per_block = (tiles + CT_MAX_BLOCKS - 1) / CT_MAX_BLOCKS;
-        const int blocks = (tiles + per_block - 1) / per_block;
-        hipLaunchKernelGGL(k_columns_scatter, dim3(blocks), dim3(CTPB), 0, c->stream, c->xm[c->cur] + c->in_off, c->vf[c->cur] + c->in_off,
-                           N, per_block, *p, g);
+    const SphLive in = sph_live(c);
+    if (in.N > 0) {
+        const SphWalk w = sph_observe_walk(in.N, CTPB, CT_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_columns_scatter, dim3(w.blocks), dim3(CTPB), 0, c->stream, in.xm, in.vf, in.N, w.per_block, *p, g);
         SPH_LAUNCH_CHECK(c);
     }
     hipLaunchKernelGGL(k_columns_finish, dim3(map_blocks), dim3(CTPB), 0, c->stream, g);
@@ -302,9 +267,7 @@ int32_t sph_columns_download(SphContext* c, int64_t* count, int64_t* sum_v, floa
     if (sum_v) SPH_HIP(c, hipMemcpyAsync(sum_v, s->sum_v, 3 * nc * 8, hipMemcpyDeviceToHost, c->stream));
     if (top) SPH_HIP(c, hipMemcpyAsync(top, s->top, nc * 4, hipMemcpyDeviceToHost, c->stream));
     if (bottom) SPH_HIP(c, hipMemcpyAsync(bottom, s->bottom, nc * 4, hipMemcpyDeviceToHost, c->stream));
-    if (totals) SPH_HIP(c, hipMemcpyAsync(totals, s->totals, sizeof(SphColumnTotals), hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(c, hipStreamSynchronize(c->stream));
-    return sph_check_device_flags(c);
+    return sph_observe_download(c, totals, s->totals, sizeof(SphColumnTotals));
 }
 
 }  // extern "C"

@@ -12,8 +12,7 @@
 //            butterfly per wave, the four waves in wave order.
 // Every grouping is a function of N, the launch shape and the particle order alone: two calls on one state give the same bits.
 // Sums are f64 (m x is exact in f64: two 24-bit significands); extrema are order-free.
-#include <new>
-#include "sph_internal.h"
+#include "sph_observe.h"
 
 #define DTPB SPH_DIAG_THREADS
 #define DWAVES (SPH_DIAG_THREADS / 64)
@@ -46,11 +45,6 @@ __device__ __forceinline__ void row_combine(SphDiagRow& r, const SphDiagRow& s) 
     }
     r.density_min = fminf(r.density_min, s.density_min); r.density_max = fmaxf(r.density_max, s.density_max);
     r.pressure_min = fminf(r.pressure_min, s.pressure_min); r.pressure_max = fmaxf(r.pressure_max, s.pressure_max);
-}
-
-__device__ __forceinline__ long long shfl_xor_i64(long long v, int m) {
-    const int lo = __shfl_xor((int)(v & 0xffffffffll), m, 64), hi = __shfl_xor((int)(v >> 32), m, 64);
-    return ((long long)hi << 32) | (unsigned)lo;
 }
 
 // all 64 lanes active; afterwards every lane holds the wave's row (both partners of a step compute the same a + b)
@@ -185,54 +179,38 @@ __global__ __launch_bounds__(DTPB) void k_diag_finish(const SphDiagRow* __restri
     }
 }
 
-void sph_diag_release(SphContext* c) {
-    if (!c->diag) return;
-    if (c->diag->part) (void)hipFree(c->diag->part);
-    if (c->diag->out) (void)hipFree(c->diag->out);
-    delete c->diag;
-    c->diag = nullptr;
-}
+void sph_diag_release(SphContext* c) { sph_observe_release(c->diag, &SphDiag::part, &SphDiag::out); }
 
+// the state struct and its rows (n_objects is fixed for the life of a context (sph_set_params): allocated once)
 static int diag_state(SphContext* c) {
-    if (c->diag) return 0;
-    SphDiag* g = new (std::nothrow) SphDiag();
+    SphDiag* g = sph_observe_state(c->diag);
     if (!g) return sph_fail(c, SPH_E_NOMEM, "sph_diag_reduce: out of host memory");
-    g->part = nullptr; g->out = nullptr; g->have = false;
-    const size_t rows = (size_t)c->p.n_objects + 2;   // n_objects is fixed for the life of a context (sph_set_params)
-    hipError_t e = hipMalloc((void**)&g->part, (size_t)SPH_DIAG_BLOCKS * rows * sizeof(SphDiagRow));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->out, rows * sizeof(SphDiagRow));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (g->part) (void)hipFree(g->part);
-        delete g;
-        snprintf(c->err, sizeof(c->err), "sph_diag_reduce: hipMalloc of the partial rows failed: %s", hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
-    c->diag = g;
+    const size_t rows = (size_t)c->p.n_objects + 2;
+    if (!g->part)
+        if (int rc = sph_observe_alloc(c, (void**)&g->part, (size_t)SPH_DIAG_BLOCKS * rows * sizeof(SphDiagRow), "sph_diag_reduce", "the partial rows")) return rc;
+    if (!g->out)
+        if (int rc = sph_observe_alloc(c, (void**)&g->out, rows * sizeof(SphDiagRow), "sph_diag_reduce", "the result rows")) return rc;
     return 0;
 }
 
 extern "C" {
 
 int32_t sph_diag_reduce(SphContext* c) {
-    if (!c) return SPH_E_INVALID;
-    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_diag_reduce: this context is a slab rank (its ghost records would be counted twice); "
-                                                         "diagnostics are reduced on single-domain contexts only");
+    if (int rc = sph_observe_enter(c, "sph_diag_reduce", " (its ghost records would be counted twice); diagnostics are reduced on single-domain contexts only")) return rc;
     if (c->p.n_objects > SPH_DIAG_MAX_OBJECTS) {
         snprintf(c->err, sizeof(c->err), "sph_diag_reduce: %d objects, the per-block row table holds %d", c->p.n_objects, SPH_DIAG_MAX_OBJECTS);
         return SPH_E_INVALID;
     }
     if (c->acc_partial) return sph_fail(c, SPH_E_STATE, "sph_diag_reduce: the last sph_slab_forces did not write every acceleration out (see sph_download)");
-    SPH_HIP(c, hipSetDevice(c->device));
     if (int rc = diag_state(c)) return rc;
     if (int rc = sph_ensure_aux(c)) return rc;   // density / pressure of a fused step live in eos2 until somebody asks
-    const int N = c->N, n_obj = c->p.n_objects;
-    int blocks = (N + DTPB - 1) / DTPB;
+    const SphLive in = sph_live(c);
+    const int n_obj = c->p.n_objects;
+    int blocks = (in.N + DTPB - 1) / DTPB;
     if (blocks > SPH_DIAG_BLOCKS) blocks = SPH_DIAG_BLOCKS;
     if (blocks > 0) {
         const size_t lds = (size_t)DWAVES * (n_obj + 1) * sizeof(SphDiagRow);   // <= 4 * 97 * 144 B = 55,872 B
-        hipLaunchKernelGGL(k_diag_reduce, dim3(blocks), dim3(DTPB), lds, c->stream, c->xm[c->cur] + c->in_off, c->vf[c->cur] + c->in_off,
-                           c->aux[c->cur] + c->in_off, c->acc + c->in_off, N, n_obj, c->diag->part);
+        hipLaunchKernelGGL(k_diag_reduce, dim3(blocks), dim3(DTPB), lds, c->stream, in.xm, in.vf, in.aux, in.acc, in.N, n_obj, c->diag->part);
         SPH_LAUNCH_CHECK(c);
     }
     hipLaunchKernelGGL(k_diag_finish, dim3(n_obj + 1), dim3(DTPB), 0, c->stream, c->diag->part, blocks, n_obj, c->diag->out);
@@ -245,10 +223,7 @@ int32_t sph_diag_download(SphContext* c, SphDiagRow* rows, int32_t n_rows) {
     if (!c) return SPH_E_INVALID;
     if (!c->diag || !c->diag->have) return sph_fail(c, SPH_E_STATE, "sph_diag_download: nothing has been reduced (call sph_diag_reduce first)");
     if (!rows || n_rows != c->p.n_objects + 1) return sph_fail(c, SPH_E_INVALID, "sph_diag_download: n_rows must be n_objects + 1 (one row per object, then all particles)");
-    SPH_HIP(c, hipSetDevice(c->device));
-    SPH_HIP(c, hipMemcpyAsync(rows, c->diag->out, (size_t)n_rows * sizeof(SphDiagRow), hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(c, hipStreamSynchronize(c->stream));
-    return sph_check_device_flags(c);
+    return sph_observe_download(c, rows, c->diag->out, (size_t)n_rows * sizeof(SphDiagRow));
 }
 
 }  // extern "C"

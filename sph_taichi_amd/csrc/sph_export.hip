@@ -23,9 +23,8 @@
 // Determinism: which record marks a slot does not depend on order or scheduling while the ids are unique (one writer per slot), and
 // every later stage is a function of the table alone.
 #include <cmath>
-#include <new>
 #include <stdlib.h>
-#include "sph_internal.h"
+#include "sph_observe.h"
 
 #define SPH_EXPORT_TILE 1024   // table slots per workgroup of k_export_count / k_export_pack
 #define ETPB 256
@@ -33,8 +32,6 @@
 #define E_MARK_MAX_BLOCKS 2048
 #define E_MAX_WORDS 11         // x y z, vx vy vz, density, pressure, mass, id, object
 #define E_ALL_FIELDS (SPH_EXPORT_X | SPH_EXPORT_V | SPH_EXPORT_DENSITY | SPH_EXPORT_PRESSURE | SPH_EXPORT_MASS | SPH_EXPORT_ID | SPH_EXPORT_OBJECT)
-
-typedef unsigned long long u64;
 
 struct SphExport {
     int* table;          // one allocation: slot[table_len], tile_count[n_tiles], tile_offset[n_tiles], counters[4]
@@ -218,36 +215,21 @@ __global__ __launch_bounds__(ETPB) void k_export_pack(const float4* __restrict__
     }
 }
 
-void sph_export_release(SphContext* c) {
-    if (!c->exporter) return;
-    if (c->exporter->table) (void)hipFree(c->exporter->table);
-    if (c->exporter->out) (void)hipFree(c->exporter->out);
-    delete c->exporter;
-    c->exporter = nullptr;
-}
+void sph_export_release(SphContext* c) { sph_observe_release(c->exporter, &SphExport::table, &SphExport::out); }
 
 // the state struct and the table (cold_cap is fixed for the life of a context: allocated once), and an output buffer of at least `bytes`
 static int export_state(SphContext* c, size_t bytes) {
-    if (!c->exporter) {
-        SphExport* g = new (std::nothrow) SphExport();
-        if (!g) return sph_fail(c, SPH_E_NOMEM, "sph_export_select: out of host memory");
-        memset(g, 0, sizeof(*g));
+    const bool first = !c->exporter;
+    SphExport* g = sph_observe_state(c->exporter);
+    if (!g) return sph_fail(c, SPH_E_NOMEM, "sph_export_select: out of host memory");
+    if (first) {
         const char* e = getenv("SPH_EXPORT_PACK");   // A/B aid of tools/export_timing.py: per-lane row stores instead of the LDS stage
         g->direct = e && strcmp(e, "direct") == 0;
-        c->exporter = g;
     }
-    SphExport* g = c->exporter;
     if (!g->table) {
         const int n_tiles = (c->cold_cap + SPH_EXPORT_TILE - 1) / SPH_EXPORT_TILE;
         const size_t len = (size_t)n_tiles * SPH_EXPORT_TILE, words = len + (size_t)2 * n_tiles + 4;
-        void* buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, words * 4);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            snprintf(c->err, sizeof(c->err), "sph_export_select: hipMalloc of the id table (%zu bytes) failed: %s", words * 4, hipGetErrorString(e));
-            return SPH_E_NOMEM;
-        }
-        g->table = (int*)buf;
+        if (int rc = sph_observe_alloc(c, (void**)&g->table, words * 4, "sph_export_select", "the id table")) return rc;
         g->tile_count = g->table + len;
         g->tile_offset = g->tile_count + n_tiles;
         g->counters = (unsigned*)(g->tile_offset + n_tiles);
@@ -255,19 +237,8 @@ static int export_state(SphContext* c, size_t bytes) {
         g->n_tiles = n_tiles;
     }
     if (bytes > g->out_bytes) {
-        if (g->out) {
-            SPH_HIP(c, hipStreamSynchronize(c->stream));   // an earlier select may still be writing the rows
-            (void)hipFree(g->out);
-            g->out = nullptr; g->out_bytes = 0; g->have = false;
-        }
-        void* buf = nullptr;
-        const hipError_t e = hipMalloc(&buf, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            snprintf(c->err, sizeof(c->err), "sph_export_select: hipMalloc of the row buffer (%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-            return SPH_E_NOMEM;
-        }
-        g->out = buf;
+        g->out_bytes = 0; g->have = false;   // (an earlier select may still be writing the rows: the helper waits for it)
+        if (int rc = sph_observe_alloc(c, &g->out, bytes, "sph_export_select", "the row buffer")) return rc;
         g->out_bytes = bytes;
     }
     return 0;
@@ -280,23 +251,17 @@ static int export_fetch(SphContext* c, const char* who) {
         snprintf(c->err, sizeof(c->err), "%s: nothing has been selected (call sph_export_select first)", who);
         return SPH_E_STATE;
     }
-    SPH_HIP(c, hipSetDevice(c->device));
-    if (!s->fetched) {
-        SPH_HIP(c, hipMemcpyAsync(s->host_counters, s->counters, sizeof(s->host_counters), hipMemcpyDeviceToHost, c->stream));
-        SPH_HIP(c, hipStreamSynchronize(c->stream));
-        s->fetched = true;
-        if (int rc = sph_check_device_flags(c)) return rc;
-    }
-    return 0;
+    if (s->fetched) return 0;
+    const int rc = sph_observe_download(c, s->host_counters, s->counters, sizeof(s->host_counters));
+    s->fetched = rc <= 0;   // (a HIP error is positive: the counters did not arrive)
+    return rc;
 }
 
 extern "C" {
 
 int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
-    if (!c) return SPH_E_INVALID;
-    if (!p) return sph_fail(c, SPH_E_INVALID, "sph_export_select: params is NULL");
-    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_export_select: this context is a slab rank (its ghost records would be exported twice); "
-                                                         "particles are exported from single-domain contexts only");
+    if (c && !p) return sph_fail(c, SPH_E_INVALID, "sph_export_select: params is NULL");
+    if (int rc = sph_observe_enter(c, "sph_export_select", " (its ghost records would be exported twice); particles are exported from single-domain contexts only")) return rc;
     if (!(p->fields & SPH_EXPORT_X)) return sph_fail(c, SPH_E_INVALID, "sph_export_select: fields must hold SPH_EXPORT_X (the position is always exported)");
     if (p->fields & ~E_ALL_FIELDS) return sph_fail(c, SPH_E_INVALID, "sph_export_select: fields holds unknown bits");
     if (p->n_objects < 0 || p->n_objects > SPH_EXPORT_MAX_OBJECTS) {
@@ -311,22 +276,17 @@ int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
             if (p->box_lo[a] > p->box_hi[a]) return sph_fail(c, SPH_E_INVALID, "sph_export_select: box_lo must not exceed box_hi");
         }
     }
-    SPH_HIP(c, hipSetDevice(c->device));
     const int N = c->N, row_words = export_row_words(p->fields);
     if (int rc = export_state(c, (size_t)(N > 0 ? N : 1) * row_words * 4)) return rc;
     if (p->fields & (SPH_EXPORT_DENSITY | SPH_EXPORT_PRESSURE))
         if (int rc = sph_ensure_aux(c)) return rc;   // density / pressure of a fused step live in eos2 until somebody asks
     SphExport* s = c->exporter;
-    const float4* xm = c->xm[c->cur] + c->in_off;
-    const float4* vf = c->vf[c->cur] + c->in_off;
-    const float4* aux = c->aux[c->cur] + c->in_off;
+    const SphLive in = sph_live(c);
     hipLaunchKernelGGL(k_export_clear, dim3(s->table_len / ETPB), dim3(ETPB), 0, c->stream, s->table, s->table_len, s->counters);
     SPH_LAUNCH_CHECK(c);
     if (N > 0) {
-        const int tiles = (N + ETPB - 1) / ETPB;
-        const int per_block = (tiles + E_MARK_MAX_BLOCKS - 1) / E_MARK_MAX_BLOCKS;
-        const int blocks = (tiles + per_block - 1) / per_block;
-        hipLaunchKernelGGL(k_export_mark, dim3(blocks), dim3(ETPB), 0, c->stream, xm, vf, aux, N, c->cold_cap, per_block, *p, s->table, s->counters);
+        const SphWalk w = sph_observe_walk(N, ETPB, E_MARK_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_export_mark, dim3(w.blocks), dim3(ETPB), 0, c->stream, in.xm, in.vf, in.aux, N, c->cold_cap, w.per_block, *p, s->table, s->counters);
         SPH_LAUNCH_CHECK(c);
     }
     hipLaunchKernelGGL(k_export_count, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, s->table, s->tile_count);
@@ -335,10 +295,10 @@ int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
     SPH_LAUNCH_CHECK(c);
     if (N > 0) {
         if (s->direct)
-            hipLaunchKernelGGL(k_export_pack<false>, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, xm, vf, aux, N, s->table, s->tile_offset, p->fields,
+            hipLaunchKernelGGL(k_export_pack<false>, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, in.xm, in.vf, in.aux, N, s->table, s->tile_offset, p->fields,
                                row_words, N, (unsigned*)s->out);
         else
-            hipLaunchKernelGGL(k_export_pack<true>, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, xm, vf, aux, N, s->table, s->tile_offset, p->fields,
+            hipLaunchKernelGGL(k_export_pack<true>, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, in.xm, in.vf, in.aux, N, s->table, s->tile_offset, p->fields,
                                row_words, N, (unsigned*)s->out);
         SPH_LAUNCH_CHECK(c);
     }
@@ -377,9 +337,7 @@ int32_t sph_export_download(SphContext* c, void* host, size_t bytes) {
         return SPH_E_INVALID;
     }
     if (want == 0) return 0;
-    SPH_HIP(c, hipMemcpyAsync(host, s->out, want, hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(c, hipStreamSynchronize(c->stream));
-    return sph_check_device_flags(c);
+    return sph_observe_download(c, host, s->out, want);
 }
 
 }  // extern "C"

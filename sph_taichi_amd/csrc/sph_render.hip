@@ -5,13 +5,15 @@
 //
 // Launches per frame (all on the context's stream; particle state is read, never written):
 //   k_render_clear    every pixel key = 0xFFFFFFFF'00000000 | background; the large-sprite counter = 0
-//   k_render_splat    one lane per particle: sprites of pixel radius <= SPH_RENDER_SMALL_R are rasterised by their lane,
-//                     larger ones are appended to a compacted index list (in the context's staging buffer, which is idle
-//                     between an upload / download and the next); the launch's LAST blocks rasterise the box edges,
+//   k_frame_splat<LAYER_ALL>  one lane per particle: sprites of pixel radius <= SPH_RENDER_SMALL_R are rasterised by their
+//                     lane, larger ones are appended to a compacted index list (in the context's staging buffer, which is
+//                     idle between an upload / download and the next); the launch's LAST blocks rasterise the box edges,
 //                     one lane per sample
-//   k_render_large    one WAVE per listed particle, lanes striding over the sprite's bounding box (grid-stride over the
-//                     list: the count never visits the host)
+//   k_frame_large<LAYER_ALL>  one WAVE per listed particle, lanes striding over the sprite's bounding box (grid-stride over
+//                     the list: the count never visits the host)
 //   k_render_resolve  keys -> u8 [H, W, 3] and f32 depth [H, W]
+// The two splat kernels are templates over the LAYER of particles they draw (sph_render_dev.h); this file holds their only
+// instances, and frame_enqueue_layer launches them for the surface frame's two layers (sph_surface.hip) as well.
 // Every loop is bounded: the bounding box is clamped to the image and to SPH_RENDER_MAX_R pixels around the centre (a
 // sprite larger than that is cropped to that square), particles inside the near plane or with a non-finite projection
 // are culled.
@@ -59,7 +61,6 @@
 //   i = int(px), j = int(py);  key = bits(zc) << 32 | box rgb, box rgb[k] = uint(min(max(box_color[k], 0), 1) * 255 + 0.5)
 // Resolve: rgb = low 24 bits of the key; depth = float of the high 32 bits, +inf where they are 0xFFFFFFFF.
 #include <math.h>
-#include <new>
 
 #include "sph_render_dev.h"   // RenderCam, SphRender, the sprite / fragment / box-edge device functions (shared with sph_surface.hip)
 
@@ -72,18 +73,32 @@ __global__ __launch_bounds__(RTPB) void k_render_clear(unsigned long long* __res
     if (i < n_pix) keys[i] = 0xFFFFFFFF00000000ull | background;
 }
 
-// blocks [0, particle_blocks): one lane per particle; blocks behind them: one lane per box-edge sample
-__global__ __launch_bounds__(RTPB) void k_render_splat(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ vf,
-                                                       const float4* __restrict__ aux, const int* __restrict__ color_cold, int N,
-                                                       int cold_cap, int particle_blocks, unsigned long long* __restrict__ keys,
-                                                       int* __restrict__ big_list, unsigned* __restrict__ big_count, int big_cap) {
+// does LAYER draw the particle with these flags?
+template <int LAYER>
+__device__ __forceinline__ bool frame_draws(const RenderCam& cam, int flags) {
+    if (LAYER != LAYER_ALL && sph_is_fluid(flags) != (LAYER == LAYER_FLUID)) return false;
+    return render_visible(cam, flags);
+}
+
+template <int LAYER>
+__device__ __forceinline__ void frame_fragment(const RenderCam& cam, const FramePlanes& g, const Sprite& s, const float kc[3], int i, int j) {
+    if (LAYER == LAYER_FLUID) surface_fragment(cam, g.keys, g.fz, g.thick, s, i, j);
+    else render_fragment(cam, g.keys, s, kc, i, j);
+}
+
+// blocks [0, particle_blocks): one lane per particle; blocks behind them (none for LAYER_FLUID): one lane per box-edge sample
+template <int LAYER>
+__global__ __launch_bounds__(RTPB) void k_frame_splat(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ vf,
+                                                      const float4* __restrict__ aux, const int* __restrict__ color_cold, int N,
+                                                      int cold_cap, int particle_blocks, FramePlanes g, int* __restrict__ big_list,
+                                                      unsigned* __restrict__ big_count, int big_cap) {
     if ((int)blockIdx.x >= particle_blocks) {
-        render_box_sample(cam, keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
+        if (LAYER != LAYER_FLUID) render_box_sample(cam, g.keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
         return;
     }
     const int p = blockIdx.x * RTPB + threadIdx.x;
     if (p >= N) return;
-    if (!render_visible(cam, __float_as_int(vf[p].w))) return;
+    if (!frame_draws<LAYER>(cam, __float_as_int(vf[p].w))) return;
     const float4 x = xm[p];
     Sprite s;
     if (!render_sprite(cam, x.x, x.y, x.z, s)) return;
@@ -92,16 +107,17 @@ __global__ __launch_bounds__(RTPB) void k_render_splat(RenderCam cam, const floa
         if (slot < (unsigned)big_cap) big_list[slot] = p;    // (each particle is listed at most once and big_cap >= N)
         return;
     }
-    float kc[3];
-    render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+    float kc[3] = {0.0f, 0.0f, 0.0f};
+    if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
     for (int j = s.j0; j <= s.j1; ++j)           // at most 9 x 9: R <= SPH_RENDER_SMALL_R
-        for (int i = s.i0; i <= s.i1; ++i) render_fragment(cam, keys, s, kc, i, j);
+        for (int i = s.i0; i <= s.i1; ++i) frame_fragment<LAYER>(cam, g, s, kc, i, j);
 }
 
-__global__ __launch_bounds__(RTPB) void k_render_large(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ aux,
-                                                       const int* __restrict__ color_cold, int N, int cold_cap,
-                                                       unsigned long long* __restrict__ keys, const int* __restrict__ big_list,
-                                                       const unsigned* __restrict__ big_count, int big_cap) {
+template <int LAYER>
+__global__ __launch_bounds__(RTPB) void k_frame_large(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ aux,
+                                                      const int* __restrict__ color_cold, int N, int cold_cap, FramePlanes g,
+                                                      const int* __restrict__ big_list, const unsigned* __restrict__ big_count,
+                                                      int big_cap) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * RTPB + threadIdx.x) >> 6, n_waves = (gridDim.x * RTPB) >> 6;
     unsigned n = *big_count;
@@ -112,12 +128,12 @@ __global__ __launch_bounds__(RTPB) void k_render_large(RenderCam cam, const floa
         const float4 x = xm[p];
         Sprite s;
         if (!render_sprite(cam, x.x, x.y, x.z, s)) continue;
-        float kc[3];
-        render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+        float kc[3] = {0.0f, 0.0f, 0.0f};
+        if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
         const int bw = s.i1 - s.i0 + 1, bh = s.j1 - s.j0 + 1;   // each <= 2 * SPH_RENDER_MAX_R + 1
         for (int t = lane; t < bw * bh; t += 64) {
             const int jj = t / bw;
-            render_fragment(cam, keys, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
+            frame_fragment<LAYER>(cam, g, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
         }
     }
 }
@@ -125,13 +141,7 @@ __global__ __launch_bounds__(RTPB) void k_render_large(RenderCam cam, const floa
 __global__ __launch_bounds__(RTPB) void k_render_resolve(const unsigned long long* __restrict__ keys, int n_pix,
                                                          unsigned char* __restrict__ rgb, float* __restrict__ depth) {
     const int i = blockIdx.x * RTPB + threadIdx.x;
-    if (i >= n_pix) return;
-    const unsigned long long k = keys[i];
-    const unsigned hi = (unsigned)(k >> 32), lo = (unsigned)k;
-    rgb[3 * (size_t)i + 0] = (unsigned char)(lo >> 16);
-    rgb[3 * (size_t)i + 1] = (unsigned char)(lo >> 8);
-    rgb[3 * (size_t)i + 2] = (unsigned char)lo;
-    depth[i] = hi == 0xFFFFFFFFu ? __uint_as_float(0x7F800000u) : __uint_as_float(hi);
+    if (i < n_pix) depth[i] = render_resolve_key(keys[i], rgb + 3 * (size_t)i);
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
@@ -196,65 +206,56 @@ static const char* make_camera(const SphRenderParams& p, RenderCam& cam) {
     return nullptr;
 }
 
-static void render_free_buffers(SphRender* r) {
-    if (r->keys) (void)hipFree(r->keys);
-    if (r->big_count) (void)hipFree(r->big_count);
-    if (r->rgb) (void)hipFree(r->rgb);
-    if (r->depth) (void)hipFree(r->depth);
-    r->keys = nullptr; r->big_count = nullptr; r->rgb = nullptr; r->depth = nullptr;
-    r->W = r->H = 0;
-    r->have_frame = false;
-}
-
-void sph_render_release(SphContext* c) {
-    if (!c->render) return;
-    render_free_buffers(c->render);
-    delete c->render;
-    c->render = nullptr;
-}
-
-// compositing across GPUs is not built: a context that holds a window of the domain refuses
-static bool render_is_slab(const SphContext* c) { return sph_is_slab(c); }
-
-static SphRender* render_state(SphContext* c) {
-    if (!c->render) {
-        c->render = new (std::nothrow) SphRender();
-        if (c->render) memset(c->render, 0, sizeof(SphRender));
-    }
-    return c->render;
-}
+void sph_render_release(SphContext* c) { sph_observe_release(c->render, &SphRender::block); }
 
 static int render_alloc(SphContext* c, SphRender* r) {
     const int W = r->cam.W, H = r->cam.H;
-    if (r->keys && r->W == W && r->H == H) return 0;
-    if (r->keys) {   // another size: the old buffers may still be read by an enqueued frame
-        SPH_HIP(c, hipStreamSynchronize(c->stream));
-        render_free_buffers(r);
-    }
-    const size_t n = (size_t)W * H;
-    hipError_t e = hipMalloc((void**)&r->keys, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->big_count, 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->rgb, n * 3);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->depth, n * 4);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        render_free_buffers(r);
-        snprintf(c->err, sizeof(c->err), "sph_render_frame: hipMalloc of the %d x %d frame buffers failed: %s", W, H, hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
+    if (r->block && r->W == W && r->H == H) return 0;
+    r->W = r->H = 0; r->have_frame = false;
+    const size_t n = (size_t)W * H, rgb_bytes = (3 * n + 15) & ~(size_t)15;
+    if (int rc = sph_observe_alloc(c, &r->block, 12 * n + rgb_bytes + 16, "sph_render_frame", "the frame buffers")) return rc;
+    char* b = (char*)r->block;
+    r->keys = (unsigned long long*)b; b += 8 * n;
+    r->depth = (float*)b; b += 4 * n;
+    r->rgb = (unsigned char*)b; b += rgb_bytes;
+    r->big_count = (unsigned*)b;
     r->W = W; r->H = H;
     return 0;
 }
 
+template <int LAYER>
+int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count) {
+    const SphLive in = sph_live(c);
+    int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity; the previous layer's large launch is ahead on the stream
+    const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
+    const int particle_blocks = (in.N + RTPB - 1) / RTPB;
+    const int box_blocks = LAYER != LAYER_FLUID && cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
+    if (particle_blocks + box_blocks > 0) {
+        hipLaunchKernelGGL(k_frame_splat<LAYER>, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.vf, in.aux,
+                           c->color_cold, in.N, c->cold_cap, particle_blocks, planes, big_list, big_count, big_cap);
+        SPH_LAUNCH_CHECK(c);
+    }
+    if (in.N > 0) {
+        int blocks = (in.N + 3) / 4;          // one wave per listed particle, at most 4096 waves striding over the list
+        if (blocks > 1024) blocks = 1024;
+        hipLaunchKernelGGL(k_frame_large<LAYER>, dim3(blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.aux, c->color_cold, in.N, c->cold_cap,
+                           planes, big_list, big_count, big_cap);
+        SPH_LAUNCH_CHECK(c);
+    }
+    return 0;
+}
+template int frame_enqueue_layer<LAYER_ALL>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
+template int frame_enqueue_layer<LAYER_OPAQUE>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
+template int frame_enqueue_layer<LAYER_FLUID>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
+
 extern "C" {
 
 int32_t sph_render_set_params(SphContext* c, const SphRenderParams* params) {
-    if (!c) return SPH_E_INVALID;
-    if (!params) return sph_fail(c, SPH_E_INVALID, "sph_render_set_params: null argument");
-    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_set_params: this context is a slab rank; frames are rendered from single-domain contexts only");
+    if (c && !params) return sph_fail(c, SPH_E_INVALID, "sph_render_set_params: null argument");
+    if (int rc = sph_observe_enter(c, "sph_render_set_params", FRAME_SLAB_WHY)) return rc;
     RenderCam cam;
     if (const char* what = make_camera(*params, cam)) return sph_fail(c, SPH_E_INVALID, what);
-    SphRender* r = render_state(c);
+    SphRender* r = sph_observe_state(c->render);
     if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_render_set_params: out of host memory");
     cam.n_invisible = r->cam.n_invisible;
     memcpy(cam.invisible, r->cam.invisible, sizeof(cam.invisible));
@@ -267,8 +268,8 @@ int32_t sph_render_set_invisible(SphContext* c, const int32_t* object_ids, int32
     if (!c) return SPH_E_INVALID;
     if (n < 0 || n > SPH_RENDER_MAX_INVISIBLE || (n > 0 && !object_ids))
         return sph_fail(c, SPH_E_INVALID, "sph_render_set_invisible: n must be in [0, 32] with a list behind it");
-    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_set_invisible: this context is a slab rank; frames are rendered from single-domain contexts only");
-    SphRender* r = render_state(c);
+    if (int rc = sph_observe_enter(c, "sph_render_set_invisible", FRAME_SLAB_WHY)) return rc;
+    SphRender* r = sph_observe_state(c->render);
     if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_render_set_invisible: out of host memory");
     r->cam.n_invisible = n;
     for (int k = 0; k < n; ++k) r->cam.invisible[k] = object_ids[k];
@@ -276,36 +277,15 @@ int32_t sph_render_set_invisible(SphContext* c, const int32_t* object_ids, int32
 }
 
 int32_t sph_render_frame(SphContext* c) {
-    if (!c) return SPH_E_INVALID;
-    if (render_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_render_frame: this context is a slab rank; frames are rendered from single-domain contexts only");
+    if (int rc = sph_observe_enter(c, "sph_render_frame", FRAME_SLAB_WHY)) return rc;
     SphRender* r = c->render;
     if (!r || r->cam.W <= 0) return sph_fail(c, SPH_E_STATE, "sph_render_frame needs sph_render_set_params first");
-    SPH_HIP(c, hipSetDevice(c->device));
     if (int rc = render_alloc(c, r)) return rc;
     const RenderCam& cam = r->cam;
     const int n_pix = cam.W * cam.H;     // <= 2^28
-    const int N = c->N;
-    const float4* xm = c->xm[c->cur] + c->in_off;
-    const float4* vf = c->vf[c->cur] + c->in_off;
-    const float4* aux = c->aux[c->cur] + c->in_off;
-    int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity
-    const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
     hipLaunchKernelGGL(k_render_clear, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, cam.background, r->big_count);
     SPH_LAUNCH_CHECK(c);
-    const int particle_blocks = (N + RTPB - 1) / RTPB;
-    const int box_blocks = cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
-    if (particle_blocks + box_blocks > 0) {
-        hipLaunchKernelGGL(k_render_splat, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, xm, vf, aux, c->color_cold, N,
-                           c->cold_cap, particle_blocks, r->keys, big_list, r->big_count, big_cap);
-        SPH_LAUNCH_CHECK(c);
-    }
-    if (N > 0) {
-        int blocks = (N + 3) / 4;          // one wave per listed particle, at most 4096 waves striding over the list
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(k_render_large, dim3(blocks), dim3(RTPB), 0, c->stream, cam, xm, aux, c->color_cold, N, c->cold_cap, r->keys,
-                           big_list, r->big_count, big_cap);
-        SPH_LAUNCH_CHECK(c);
-    }
+    if (int rc = frame_enqueue_layer<LAYER_ALL>(c, cam, FramePlanes{r->keys, nullptr, nullptr}, r->big_count)) return rc;
     hipLaunchKernelGGL(k_render_resolve, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, r->rgb, r->depth);
     SPH_LAUNCH_CHECK(c);
     r->have_frame = true;
@@ -318,10 +298,7 @@ static int render_download(SphContext* c, void* host, size_t bytes, bool depth) 
     if (!r || !r->have_frame) return sph_fail(c, SPH_E_STATE, "sph_render_download: no frame has been rendered");
     const size_t want = (size_t)r->W * r->H * (depth ? 4 : 3);
     if (!host || bytes != want) return sph_fail(c, SPH_E_INVALID, "sph_render_download: size mismatch (u8 [H, W, 3] / f32 [H, W] of the last frame)");
-    SPH_HIP(c, hipSetDevice(c->device));
-    SPH_HIP(c, hipMemcpyAsync(host, depth ? (const void*)r->depth : (const void*)r->rgb, bytes, hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(c, hipStreamSynchronize(c->stream));
-    return sph_check_device_flags(c);
+    return sph_observe_download(c, host, depth ? (const void*)r->depth : (const void*)r->rgb, bytes);
 }
 
 int32_t sph_render_download(SphContext* c, uint8_t* rgb, size_t bytes) { return render_download(c, rgb, bytes, false); }

@@ -1,10 +1,11 @@
-// sph_render_dev.h -- the camera record and the sprite / fragment / box-edge device functions of the frame export, shared by
-// the sphere frame (sph_render.hip, whose comment block states their arithmetic) and the surface frame (sph_surface.hip,
-// whose opaque layer is the same picture restricted to the particles that are not fluid).
+// sph_render_dev.h -- the camera record, the sprite / fragment / box-edge device functions and the splat of one LAYER of
+// particles, shared by the sphere frame (sph_render.hip, whose comment block states their arithmetic and which holds the splat
+// kernels) and the surface frame (sph_surface.hip: its opaque layer is the sphere frame's picture restricted to the particles
+// that are not fluid, its fluid layer the same sprites with another fragment).
 #pragma once
 #include <math.h>
 
-#include "sph_internal.h"
+#include "sph_observe.h"
 
 #pragma clang fp contract(off)
 
@@ -12,6 +13,7 @@
 #define SPH_RENDER_MAX_R 512.0f    // larger sprites are cropped to the square of this half-width around their centre
 #define SPH_RENDER_MAX_DIM 16384
 #define RTPB 256
+#define FRAME_SLAB_WHY "; frames are rendered from single-domain contexts only"   // sph_observe_enter: compositing across GPUs is not built
 
 struct RenderCam {
     int W, H, S;              // image size; samples per box edge
@@ -29,15 +31,31 @@ struct RenderCam {
 struct SphRender {
     SphRenderParams p;
     RenderCam cam;
-    int W, H;                              // what the buffers below are sized for
+    int W, H;                              // what the block below is sized for
+    void* block;                           // one allocation, carved into:
     unsigned long long* keys;              // [W * H]
-    unsigned* big_count;                   // device counter of the large-sprite list
-    unsigned char* rgb;                    // [H * W * 3]
     float* depth;                          // [H * W]
+    unsigned char* rgb;                    // [H * W * 3]
+    unsigned* big_count;                   // device counter of the large-sprite list
     bool have_frame;
 };
 
 struct Sprite { float a, b, zc, px, py, inv; int i0, i1, j0, j1; float R; };
+
+// Which particles a splat draws, and into what: every visible one or the visible ones that are not fluid as shaded spheres into
+// the min-key plane (with the box edges), or the visible fluid ones into the fluid depth / thickness planes.
+enum FrameLayer { LAYER_ALL, LAYER_OPAQUE, LAYER_FLUID };
+
+struct FramePlanes {                       // by value; a layer touches only its own
+    unsigned long long* keys;              // min-keys: written by LAYER_ALL / LAYER_OPAQUE, read (final by then) by LAYER_FLUID
+    unsigned* fz;                          // LAYER_FLUID: fluid depth bits
+    unsigned* thick;                       // LAYER_FLUID: thickness sums
+};
+
+// Enqueues one layer on the context's stream (sph_render.hip): k_frame_splat<LAYER>, then k_frame_large<LAYER> over the sprites
+// the first one listed through `big_count`, a device counter the frame's clear kernel has zeroed.
+template <int LAYER>
+int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float rdot(float ax, float ay, float az, float dx, float dy, float dz) { return (ax * dx + ay * dy) + az * dz; }
@@ -93,6 +111,31 @@ __device__ __forceinline__ void render_fragment(const RenderCam& cam, unsigned l
     const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | rgb;
     unsigned long long* p = keys + (size_t)j * cam.W + i;      // 0 <= i < W, 0 <= j < H by the clamped box
     if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+}
+
+// the fluid layer's fragment (sph_surface.hip states its arithmetic): the same sphere, its depth and chord instead of a colour
+__device__ __forceinline__ void surface_fragment(const RenderCam& cam, const unsigned long long* __restrict__ keys,
+                                                 unsigned* __restrict__ fz, unsigned* __restrict__ thick, const Sprite& s, int i, int j) {
+    const float dx = (((float)i + 0.5f) - s.px) * s.inv;
+    const float dy = (s.py - ((float)j + 0.5f)) * s.inv;
+    const float h2 = (cam.r2 - dx * dx) - dy * dy;
+    if (!(h2 >= 0.0f)) return;
+    const float hh = sqrtf(h2);
+    const float z = s.zc - hh;
+    if (!(z > 0.0f)) return;
+    const size_t p = (size_t)j * cam.W + i;                    // 0 <= i < W, 0 <= j < H by the clamped box
+    const unsigned zb = __float_as_uint(z);
+    if (zb < __hip_atomic_load(fz + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(fz + p, zb);
+    if (zb < (unsigned)(keys[p] >> 32)) atomicAdd(thick + p, (unsigned)((hh / cam.radius) * 256.0f + 0.5f));   // (the opaque layer is final)
+}
+
+// a resolved min-key: its colour bytes into rgb[0 .. 2]; returns its depth, +inf where nothing was drawn
+__device__ __forceinline__ float render_resolve_key(unsigned long long key, unsigned char* __restrict__ rgb) {
+    const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
+    rgb[0] = (unsigned char)(lo >> 16);
+    rgb[1] = (unsigned char)(lo >> 8);
+    rgb[2] = (unsigned char)lo;
+    return hi == 0xFFFFFFFFu ? __uint_as_float(0x7F800000u) : __uint_as_float(hi);
 }
 
 __device__ __forceinline__ void render_colour(const int* __restrict__ color_cold, int pid, int cold_cap, float kc[3]) {

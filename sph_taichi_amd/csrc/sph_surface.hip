@@ -7,13 +7,14 @@
 // Launches per frame (all on the context's stream; particle state is read, never written; n = width * height pixels):
 //   k_surface_clear         keys = 0xFFFFFFFF'00000000 | background, fluid depth bits = 0xFFFFFFFF, thickness sum = 0, both
 //                           large-sprite counters = 0                                                        writes 16 n B
-//   k_surface_splat<false>  one lane per particle that is visible and NOT fluid: small sprites rasterised by their lane into
-//                           the 64-bit min-key plane, large ones listed; the launch's last blocks: the box edges
-//   k_surface_large<false>  one wave per listed sprite                                 (32 B per particle read: xm, vf; aux + colour
+//   k_frame_splat<LAYER_OPAQUE>  one lane per particle that is visible and NOT fluid: small sprites rasterised by their lane
+//                           into the 64-bit min-key plane, large ones listed; the launch's last blocks: the box edges
+//   k_frame_large<LAYER_OPAQUE>  one wave per listed sprite                            (32 B per particle read: xm, vf; aux + colour
 //                                                                                       of the drawn ones; atomics per fragment)
-//   k_surface_splat<true>   the same split over the visible FLUID particles: per fragment a u32 atomicMin into the fluid depth
-//   k_surface_large<true>   and, in front of the (now final) opaque depth, a u32 atomicAdd into the thickness sum
+//   k_frame_splat<LAYER_FLUID>   the same split over the visible FLUID particles: per fragment a u32 atomicMin into the fluid
+//   k_frame_large<LAYER_FLUID>   depth and, in front of the (now final) opaque depth, a u32 atomicAdd into the thickness sum
 //                                                                                      (32 B per particle; per fragment 8 B key read)
+//                           (the sphere frame's splat pair, sph_render.hip, enqueued per layer by frame_enqueue_layer)
 //   k_surface_smooth_depth  x iterations, ping-pong between two planes: 16 x 16 output pixels per block, the 48 x 48 window
 //                           around them staged in LDS (9216 B); per pass reads 4 n B * (48 / 16)^2 = 36 n B through the cache
 //                           hierarchy (4 n B of them new), writes 4 n B; up to 33^2 = 1089 LDS taps per pixel
@@ -80,7 +81,6 @@
 //     byte k = uint(min(max(col, 0), 1) * 255 + 0.5)                                 truncation; a NaN col gives 0
 //   depth = z;  thickness = t.
 #include <math.h>
-#include <new>
 
 #include "sph_render_dev.h"
 
@@ -127,80 +127,6 @@ __global__ __launch_bounds__(RTPB) void k_surface_clear(unsigned long long* __re
         keys[i] = 0xFFFFFFFF00000000ull | background;
         fz[i] = SURF_NONE;
         thick[i] = 0u;
-    }
-}
-
-__device__ __forceinline__ void surface_fragment(const RenderCam& cam, const unsigned long long* __restrict__ keys,
-                                                 unsigned* __restrict__ fz, unsigned* __restrict__ thick, const Sprite& s, int i, int j) {
-    const float dx = (((float)i + 0.5f) - s.px) * s.inv;
-    const float dy = (s.py - ((float)j + 0.5f)) * s.inv;
-    const float h2 = (cam.r2 - dx * dx) - dy * dy;
-    if (!(h2 >= 0.0f)) return;
-    const float hh = sqrtf(h2);
-    const float z = s.zc - hh;
-    if (!(z > 0.0f)) return;
-    const size_t p = (size_t)j * cam.W + i;                    // 0 <= i < W, 0 <= j < H by the clamped box
-    const unsigned zb = __float_as_uint(z);
-    if (zb < __hip_atomic_load(fz + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(fz + p, zb);
-    if (zb < (unsigned)(keys[p] >> 32)) atomicAdd(thick + p, (unsigned)((hh / cam.radius) * 256.0f + 0.5f));   // (the opaque layer is final)
-}
-
-// FLUID = false: blocks [0, particle_blocks) one lane per particle, the blocks behind them one lane per box-edge sample
-template <bool FLUID>
-__global__ __launch_bounds__(RTPB) void k_surface_splat(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ vf,
-                                                        const float4* __restrict__ aux, const int* __restrict__ color_cold, int N,
-                                                        int cold_cap, int particle_blocks, unsigned long long* __restrict__ keys,
-                                                        unsigned* __restrict__ fz, unsigned* __restrict__ thick,
-                                                        int* __restrict__ big_list, unsigned* __restrict__ big_count, int big_cap) {
-    if ((int)blockIdx.x >= particle_blocks) {
-        if (!FLUID) render_box_sample(cam, keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
-        return;
-    }
-    const int p = blockIdx.x * RTPB + threadIdx.x;
-    if (p >= N) return;
-    const int flags = __float_as_int(vf[p].w);
-    if (sph_is_fluid(flags) != FLUID || !render_visible(cam, flags)) return;
-    const float4 x = xm[p];
-    Sprite s;
-    if (!render_sprite(cam, x.x, x.y, x.z, s)) return;
-    if (s.R > SPH_RENDER_SMALL_R) {
-        const unsigned slot = atomicAdd(big_count, 1u);
-        if (slot < (unsigned)big_cap) big_list[slot] = p;    // (each particle is listed at most once and big_cap >= N)
-        return;
-    }
-    float kc[3] = {0.0f, 0.0f, 0.0f};
-    if (!FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
-    for (int j = s.j0; j <= s.j1; ++j)           // at most 9 x 9: R <= SPH_RENDER_SMALL_R
-        for (int i = s.i0; i <= s.i1; ++i) {
-            if (FLUID) surface_fragment(cam, keys, fz, thick, s, i, j);
-            else render_fragment(cam, keys, s, kc, i, j);
-        }
-}
-
-template <bool FLUID>
-__global__ __launch_bounds__(RTPB) void k_surface_large(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ aux,
-                                                        const int* __restrict__ color_cold, int N, int cold_cap,
-                                                        unsigned long long* __restrict__ keys, unsigned* __restrict__ fz,
-                                                        unsigned* __restrict__ thick, const int* __restrict__ big_list,
-                                                        const unsigned* __restrict__ big_count, int big_cap) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * RTPB + threadIdx.x) >> 6, n_waves = (gridDim.x * RTPB) >> 6;
-    unsigned n = *big_count;
-    if (n > (unsigned)big_cap) n = (unsigned)big_cap;
-    for (unsigned w = (unsigned)wave; w < n; w += (unsigned)n_waves) {
-        const int p = big_list[w];
-        if (p < 0 || p >= N) continue;
-        const float4 x = xm[p];
-        Sprite s;
-        if (!render_sprite(cam, x.x, x.y, x.z, s)) continue;
-        float kc[3] = {0.0f, 0.0f, 0.0f};
-        if (!FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
-        const int bw = s.i1 - s.i0 + 1, bh = s.j1 - s.j0 + 1;   // each <= 2 * SPH_RENDER_MAX_R + 1
-        for (int t = lane; t < bw * bh; t += 64) {
-            const int jj = t / bw;
-            if (FLUID) surface_fragment(cam, keys, fz, thick, s, s.i0 + (t - jj * bw), s.j0 + jj);
-            else render_fragment(cam, keys, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
-        }
     }
 }
 
@@ -298,14 +224,11 @@ __global__ __launch_bounds__(RTPB) void k_surface_resolve(RenderCam cam, SurfK s
     if (pix >= cam.W * cam.H) return;
     const int j = pix / cam.W, i = pix - j * cam.W;
     const unsigned long long key = keys[pix];
-    const unsigned hi = (unsigned)(key >> 32), lo = (unsigned)key;
-    const float zo = surf_depth(hi);
+    const unsigned lo = (unsigned)key;
+    const float zo = surf_depth((unsigned)(key >> 32));
     const float z = surf_depth(zs[pix]);
-    if (!(isfinite(z) && z < zo)) {
-        rgb[3 * (size_t)pix + 0] = (unsigned char)(lo >> 16);
-        rgb[3 * (size_t)pix + 1] = (unsigned char)(lo >> 8);
-        rgb[3 * (size_t)pix + 2] = (unsigned char)lo;
-        depth[pix] = zo;
+    if (!(isfinite(z) && z < zo)) {          // the opaque layer's pixel, as the sphere frame resolves it
+        depth[pix] = render_resolve_key(key, rgb + 3 * (size_t)pix);
         thickness[pix] = 0.0f;
         return;
     }
@@ -364,45 +287,13 @@ __global__ __launch_bounds__(RTPB) void k_surface_resolve(RenderCam cam, SurfK s
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static void surface_free_buffers(SphSurface* s) {
-    if (s->block) (void)hipFree(s->block);
-    s->block = nullptr;
-    s->keys = nullptr; s->fz = s->thick = s->plane[0] = s->plane[1] = s->counts = nullptr;
-    s->ts = s->depth = s->thickness = nullptr; s->rgb = nullptr;
-    s->W = s->H = 0;
-    s->have_frame = false;
-}
-
-void sph_surface_release(SphContext* c) {
-    if (!c->surface) return;
-    surface_free_buffers(c->surface);
-    delete c->surface;
-    c->surface = nullptr;
-}
-
-static SphSurface* surface_state(SphContext* c) {
-    if (!c->surface) {
-        c->surface = new (std::nothrow) SphSurface();
-        if (c->surface) memset(c->surface, 0, sizeof(SphSurface));
-    }
-    return c->surface;
-}
+void sph_surface_release(SphContext* c) { sph_observe_release(c->surface, &SphSurface::block); }
 
 static int surface_alloc(SphContext* c, SphSurface* s, int W, int H) {
     if (s->block && s->W == W && s->H == H) return 0;
-    if (s->block) {   // another size: the old buffers may still be read by an enqueued frame
-        SPH_HIP(c, hipStreamSynchronize(c->stream));
-        surface_free_buffers(s);
-    }
-    const size_t n = (size_t)W * H;                       // <= 2^28
-    const size_t bytes = 8 * n + 7 * 4 * n + ((3 * n + 15) & ~(size_t)15) + 16;
-    const hipError_t e = hipMalloc(&s->block, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        s->block = nullptr;
-        snprintf(c->err, sizeof(c->err), "sph_surface_frame: hipMalloc of the %d x %d frame buffers failed: %s", W, H, hipGetErrorString(e));
-        return SPH_E_NOMEM;
-    }
+    s->W = s->H = 0; s->have_frame = false;
+    const size_t n = (size_t)W * H, rgb_bytes = (3 * n + 15) & ~(size_t)15;        // n <= 2^28
+    if (int rc = sph_observe_alloc(c, &s->block, 8 * n + 7 * 4 * n + rgb_bytes + 16, "sph_surface_frame", "the frame buffers")) return rc;
     char* b = (char*)s->block;
     s->keys = (unsigned long long*)b; b += 8 * n;
     s->fz = (unsigned*)b; b += 4 * n;
@@ -412,7 +303,7 @@ static int surface_alloc(SphContext* c, SphSurface* s, int W, int H) {
     s->ts = (float*)b; b += 4 * n;
     s->depth = (float*)b; b += 4 * n;
     s->thickness = (float*)b; b += 4 * n;
-    s->rgb = (unsigned char*)b; b += (3 * n + 15) & ~(size_t)15;
+    s->rgb = (unsigned char*)b; b += rgb_bytes;
     s->counts = (unsigned*)b;
     s->W = W; s->H = H;
     return 0;
@@ -434,12 +325,11 @@ static const char* check_params(const SphSurfaceParams& p) {
 
 // the frame; ev: null, or SPH_SURFACE_PASSES + 1 events recorded around the passes
 static int surface_frame(SphContext* c, hipEvent_t* ev) {
-    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_surface_frame: this context is a slab rank; frames are rendered from single-domain contexts only");
+    if (int rc = sph_observe_enter(c, "sph_surface_frame", FRAME_SLAB_WHY)) return rc;
     const SphRender* r = c->render;
     if (!r || r->cam.W <= 0) return sph_fail(c, SPH_E_STATE, "sph_surface_frame needs the camera of the sphere frame (its set_params call) first");
     SphSurface* s = c->surface;
     if (!s || !s->have_params) return sph_fail(c, SPH_E_STATE, "sph_surface_frame needs sph_surface_set_params first");
-    SPH_HIP(c, hipSetDevice(c->device));
     const RenderCam& cam = r->cam;
     if (int rc = surface_alloc(c, s, cam.W, cam.H)) return rc;
     SurfK sk;
@@ -449,42 +339,17 @@ static int surface_frame(SphContext* c, hipEvent_t* ev) {
     for (int k = 0; k < 3; ++k) { sk.fluid[k] = s->p.fluid_color[k]; sk.absorb[k] = s->p.absorb[k]; sk.sky[k] = s->p.sky[k]; }
     sk.f0 = s->p.f0; sk.specular = s->p.specular;
     const int n_pix = cam.W * cam.H;     // <= 2^28
-    const int N = c->N;
-    const float4* xm = c->xm[c->cur] + c->in_off;
-    const float4* vf = c->vf[c->cur] + c->in_off;
-    const float4* aux = c->aux[c->cur] + c->in_off;
-    int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity; idle between an upload / download and the next
-    const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
     const int pix_blocks = (n_pix + RTPB - 1) / RTPB;
-    const int particle_blocks = (N + RTPB - 1) / RTPB;
-    const int box_blocks = cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
-    int large_blocks = (N + 3) / 4;          // one wave per listed particle, at most 4096 waves striding over the list
-    if (large_blocks > 1024) large_blocks = 1024;
+    const FramePlanes planes{s->keys, s->fz, s->thick};
     int e = 0;
 #define SURF_MARK() do { if (ev) SPH_HIP(c, hipEventRecord(ev[e++], c->stream)); } while (0)
     SURF_MARK();
     hipLaunchKernelGGL(k_surface_clear, dim3(pix_blocks), dim3(RTPB), 0, c->stream, s->keys, s->fz, s->thick, n_pix, cam.background, s->counts);
     SPH_LAUNCH_CHECK(c);
     SURF_MARK();
-    if (particle_blocks + box_blocks > 0) {
-        hipLaunchKernelGGL(k_surface_splat<false>, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, xm, vf, aux, c->color_cold,
-                           N, c->cold_cap, particle_blocks, s->keys, s->fz, s->thick, big_list, s->counts + 0, big_cap);
-        SPH_LAUNCH_CHECK(c);
-    }
-    if (N > 0) {
-        hipLaunchKernelGGL(k_surface_large<false>, dim3(large_blocks), dim3(RTPB), 0, c->stream, cam, xm, aux, c->color_cold, N, c->cold_cap,
-                           s->keys, s->fz, s->thick, big_list, s->counts + 0, big_cap);
-        SPH_LAUNCH_CHECK(c);
-    }
+    if (int rc = frame_enqueue_layer<LAYER_OPAQUE>(c, cam, planes, s->counts + 0)) return rc;
     SURF_MARK();
-    if (N > 0) {     // (the list is free again: the opaque wave-per-sprite launch is ahead on the stream)
-        hipLaunchKernelGGL(k_surface_splat<true>, dim3(particle_blocks), dim3(RTPB), 0, c->stream, cam, xm, vf, aux, c->color_cold,
-                           N, c->cold_cap, particle_blocks, s->keys, s->fz, s->thick, big_list, s->counts + 1, big_cap);
-        SPH_LAUNCH_CHECK(c);
-        hipLaunchKernelGGL(k_surface_large<true>, dim3(large_blocks), dim3(RTPB), 0, c->stream, cam, xm, aux, c->color_cold, N, c->cold_cap,
-                           s->keys, s->fz, s->thick, big_list, s->counts + 1, big_cap);
-        SPH_LAUNCH_CHECK(c);
-    }
+    if (int rc = frame_enqueue_layer<LAYER_FLUID>(c, cam, planes, s->counts + 1)) return rc;
     SURF_MARK();
     const dim3 tiles((cam.W + STILE - 1) / STILE, (cam.H + STILE - 1) / STILE);
     const unsigned* zs = s->fz;
@@ -513,20 +378,16 @@ static int surface_download(SphContext* c, void* host, size_t bytes, int which) 
     const size_t want = (size_t)s->W * s->H * (which == 0 ? 3 : 4);
     if (!host || bytes != want) return sph_fail(c, SPH_E_INVALID, "sph_surface_download: size mismatch (u8 [H, W, 3] / f32 [H, W] of the last surface frame)");
     const void* src = which == 0 ? (const void*)s->rgb : which == 1 ? (const void*)s->depth : (const void*)s->thickness;
-    SPH_HIP(c, hipSetDevice(c->device));
-    SPH_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    SPH_HIP(c, hipStreamSynchronize(c->stream));
-    return sph_check_device_flags(c);
+    return sph_observe_download(c, host, src, bytes);
 }
 
 extern "C" {
 
 int32_t sph_surface_set_params(SphContext* c, const SphSurfaceParams* params) {
-    if (!c) return SPH_E_INVALID;
-    if (!params) return sph_fail(c, SPH_E_INVALID, "sph_surface_set_params: null argument");
-    if (sph_is_slab(c)) return sph_fail(c, SPH_E_STATE, "sph_surface_set_params: this context is a slab rank; frames are rendered from single-domain contexts only");
+    if (c && !params) return sph_fail(c, SPH_E_INVALID, "sph_surface_set_params: null argument");
+    if (int rc = sph_observe_enter(c, "sph_surface_set_params", FRAME_SLAB_WHY)) return rc;
     if (const char* what = check_params(*params)) return sph_fail(c, SPH_E_INVALID, what);
-    SphSurface* s = surface_state(c);
+    SphSurface* s = sph_observe_state(c->surface);
     if (!s) return sph_fail(c, SPH_E_NOMEM, "sph_surface_set_params: out of host memory");
     s->p = *params;
     s->have_params = true;

@@ -480,11 +480,8 @@ class ParticleSystem:
         return {k[5:]: z[k] for k in z.files if k.startswith("meta_")}
 
     # ---- frame export (run_simulation.py:37-98 of the reference: the window; here an image made on the device) ----
-    def render(self, camera=None, invisible_objects=(), size=(1024, 1024)) -> np.ndarray:
-        """The particles as lit spheres of radius `particle_radius` in their objects' colours plus the domain box, seen
-        from `camera` (default: the reference's window camera), as uint8 [H, W, 3] with row 0 at the top; `size` =
-        (width, height).  Rendered on the GPU behind whatever was enqueued before; only the image is copied back.
-        Independent of `GGUI` and of `copy_to_vis_buffer`."""
+    def _set_view(self, camera, invisible_objects, size):
+        """Camera parameters and invisible list of the next frame, of either style; returns the image's (H, W)."""
         from . import render as _render
         cam = camera if camera is not None else _render.Camera()
         rp = _render.render_params(cam, size, self.particle_radius, self.domain_end)
@@ -492,21 +489,33 @@ class ParticleSystem:
         ids = [int(i) for i in invisible_objects]
         arr = (C.c_int32 * max(len(ids), 1))(*ids)
         self._call("sph_render_set_invisible", arr, len(ids))
+        return (int(size[1]), int(size[0]))
+
+    def _frame_plane(self, shape_attr, symbol, missing):
+        """float32 [H, W] plane `symbol` downloads of the last frame whose shape `shape_attr` holds."""
+        shape = getattr(self, shape_attr, None)
+        if shape is None:
+            raise _lib.SphError(missing)
+        out = np.empty(shape, dtype=np.float32)
+        self._call(symbol, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
+
+    def render(self, camera=None, invisible_objects=(), size=(1024, 1024)) -> np.ndarray:
+        """The particles as lit spheres of radius `particle_radius` in their objects' colours plus the domain box, seen
+        from `camera` (default: the reference's window camera), as uint8 [H, W, 3] with row 0 at the top; `size` =
+        (width, height).  Rendered on the GPU behind whatever was enqueued before; only the image is copied back.
+        Independent of `GGUI` and of `copy_to_vis_buffer`."""
+        shape = ParticleSystem._set_view(self, camera, invisible_objects, size)   # (by class: stand-ins borrow this method alone)
         self._call("sph_render_frame")
-        self._render_shape = (int(size[1]), int(size[0]))
-        out = np.empty(self._render_shape + (3,), dtype=np.uint8)
+        self._render_shape = shape
+        out = np.empty(shape + (3,), dtype=np.uint8)
         self._call("sph_render_download", out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
     def render_depth(self) -> np.ndarray:
         """float32 [H, W] of the last `render`: distance along the view direction of the surface (or box line) each
         pixel shows, +inf where nothing was drawn."""
-        shape = getattr(self, "_render_shape", None)
-        if shape is None:
-            raise _lib.SphError("render_depth: no frame has been rendered")
-        out = np.empty(shape, dtype=np.float32)
-        self._call("sph_render_download_depth", out.ctypes.data_as(C.c_void_p), out.nbytes)
-        return out
+        return self._frame_plane("_render_shape", "sph_render_download_depth", "render_depth: no frame has been rendered")
 
     # ---- surface frames (csrc/sph_surface.hip; the reference's window has no such style) ----
     def _first_fluid_colour(self):
@@ -520,27 +529,17 @@ class ParticleSystem:
         filter radius 3 x and the depth range 4 x the particle radius and the first fluid block's colour).  Rendered on the
         GPU behind whatever was enqueued before; only the image is copied back.  Reads the particles; changes nothing."""
         from . import render as _render
-        cam = camera if camera is not None else _render.Camera()
-        rp = _render.render_params(cam, size, self.particle_radius, self.domain_end)
-        self._call("sph_render_set_params", C.byref(rp))
-        ids = [int(i) for i in invisible_objects]
-        arr = (C.c_int32 * max(len(ids), 1))(*ids)
-        self._call("sph_render_set_invisible", arr, len(ids))
+        shape = ParticleSystem._set_view(self, camera, invisible_objects, size)   # (by class: stand-ins borrow this method alone)
         sp = _render.surface_params(_render.resolve_style(style, self.particle_radius, self._first_fluid_colour()))
         self._call("sph_surface_set_params", C.byref(sp))
         self._call("sph_surface_frame")
-        self._surface_shape = (int(size[1]), int(size[0]))
-        out = np.empty(self._surface_shape + (3,), dtype=np.uint8)
+        self._surface_shape = shape
+        out = np.empty(shape + (3,), dtype=np.uint8)
         self._call("sph_surface_download", out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
     def _surface_plane(self, symbol, what):
-        shape = getattr(self, "_surface_shape", None)
-        if shape is None:
-            raise _lib.SphError(f"{what}: no surface frame has been rendered")
-        out = np.empty(shape, dtype=np.float32)
-        self._call(symbol, out.ctypes.data_as(C.c_void_p), out.nbytes)
-        return out
+        return self._frame_plane("_surface_shape", symbol, f"{what}: no surface frame has been rendered")
 
     def render_surface_depth(self) -> np.ndarray:
         """float32 [H, W] of the last `render_surface`: the smoothed fluid depth where the fluid is shown, else the depth of

@@ -127,6 +127,36 @@ def test_no_fluid_in_the_picture_is_the_sphere_frame():
     ps.close()
 
 
+def test_the_two_styles_keep_their_own_results():
+    """The two styles run the same splat kernels with their own planes, counters and sizes: a frame of one style leaves the
+    other's last image and planes downloadable and unchanged, and changes nothing in what the other renders next.  FAR at
+    64 x 48 uses the lane-per-sprite path only, CLOSE at 250 x 130 both paths (sprite radii on both sides of the threshold)."""
+    import render_model
+    ps, solver = scenes.make_ps(scenes.fluid_with_rigid_blocks())
+    solver.initialize()
+    solver.step(5)
+    small, large = (64, 48), (250, 130)
+    spheres, sphere_depth = ps.render(FAR, size=small), ps.render_depth()
+    surface = _frame(ps, CLOSE, large)
+    assert sphere_depth.shape == (48, 64) and surface[1].shape == (130, 250)
+    assert np.array_equal(ps.render_depth().view(np.uint32), sphere_depth.view(np.uint32))      # the sphere frame's, not the surface's
+    assert np.array_equal(ps.render(FAR, size=small), spheres) and np.array_equal(ps.render_depth().view(np.uint32), sphere_depth.view(np.uint32))
+    again = (ps.render_surface_depth(), ps.render_surface_thickness())
+    buf = np.empty((130, 250, 3), np.uint8)
+    ps._call("sph_surface_download", buf.ctypes.data_as(C.c_void_p), buf.nbytes)
+    assert np.array_equal(buf, surface[0])
+    assert all(np.array_equal(p.view(np.uint32), q.view(np.uint32)) for p, q in zip(again, surface[1:]))
+    # both against their models, bound 0
+    m = _model(ps, CLOSE, large)
+    assert _same(surface, m) and m["shown"].sum() > 80
+    x, col, oid = ps.x.to_numpy(), ps.color.to_numpy(), ps.object_id.to_numpy()
+    mimg, mdepth, _ = render_model.render(x, col, oid, FAR, small, ps.particle_radius, ps.domain_end, (), np.float32)
+    assert np.array_equal(spheres, mimg) and np.array_equal(sphere_depth, mdepth.astype(np.float32)) and np.isfinite(mdepth).sum() > 80
+    radii = [s[5] for s in (render_model.sprite(render_model.Setup(CLOSE, large, ps.particle_radius, ps.domain_end), p) for p in x) if s]
+    assert min(radii) < 4.0 < max(radii)                      # SPH_RENDER_SMALL_R: both splat paths were in the surface frame
+    ps.close()
+
+
 def test_order_independence_and_reproducibility():
     sd = scenes.fluid_with_rigid_blocks()
     cfg, sc = scenes.build(sd)
