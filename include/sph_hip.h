@@ -715,6 +715,44 @@ int32_t sph_surface_download_thickness(SphContext* ctx, float* thickness, size_t
  * SPH_SURFACE_PASSES (n must equal it).  Synchronises; the frame it leaves is an ordinary one. */
 int32_t sph_surface_frame_timed(SphContext* ctx, float* ms, int32_t n);
 
+/* ======================================================================================
+ * Field colouring of the frames (no reference counterpart: its window colours a particle by its object): the SELECTED
+ * particles take a colour from a 256-entry table, indexed by a scalar field of the particle mapped linearly from [lo, hi] to
+ * 0..255; every other particle keeps its object colour.  It applies to both frame styles and stays in force until it is switched
+ * off.  csrc/sph_render.hip states the index arithmetic (binary32, no contraction), csrc/sph_surface.hip what the surface frame
+ * does with the index of the nearest fluid fragment of a pixel.
+ * SELECTED: a particle whose material equals `material` (unless -1) and whose object id is in object_ids[0..n_objects) (unless
+ * n_objects == 0).  Density and pressure that a fused step left in its own record are materialised by a frame (or a range)
+ * that needs them, as any download of them does; nothing else of the context is written.
+ * sph_frame_set_colour(ctx, NULL, NULL) switches the colouring off: frames are then made by the launches, and hold the bytes,
+ * of a context that never switched it on.  `lut`: 256 x 3 int32 in [0, 255], red green blue; it is uploaded when it differs from
+ * the one in force.
+ * sph_field_range: minimum and maximum of the field over the particles that are selected, not of an invisible object
+ * (sph_render_set_invisible) and whose field value is finite, their number, and the number of selected, visible particles whose
+ * value is NOT finite; lo / hi of `colour` are not read.  One streaming pass; the extrema travel as integers, so the result does not
+ * depend on particle order.  count == 0 gives lo = +inf, hi = -inf.  Synchronises.
+ * SPH_E_INVALID: an unknown field, material outside [-1, 255], n_objects outside [0, SPH_FIELD_MAX_OBJECTS], lo or hi not finite,
+ * lo >= hi, a range whose reciprocal width is not a positive finite binary32, a table entry outside [0, 255], one of
+ * colour / lut null and the other not.  SPH_E_STATE: a slab rank, as for the frames.
+ * ==================================================================================== */
+#define SPH_FIELD_MAX_OBJECTS 32
+enum SphColourField { SPH_FIELD_SPEED = 0, SPH_FIELD_VX, SPH_FIELD_VY, SPH_FIELD_VZ, SPH_FIELD_DENSITY, SPH_FIELD_PRESSURE,
+                      SPH_FIELD_X, SPH_FIELD_Y, SPH_FIELD_Z, SPH_FIELD_COUNT_ };
+typedef struct SphFieldColour {
+    int32_t field;                  /* enum SphColourField */
+    int32_t material;               /* -1: any; else == the particle's material */
+    int32_t n_objects;              /* 0: any object */
+    int32_t object_ids[SPH_FIELD_MAX_OBJECTS];
+    float lo, hi;                   /* the field values that map to the table's first and last entry */
+    float axis_origin;              /* subtracted from a position field (SPH_FIELD_X / _Y / _Z) before anything else */
+} SphFieldColour;
+typedef struct SphFieldRange { float lo, hi; int64_t count, non_finite; } SphFieldRange;
+int32_t sph_frame_set_colour(SphContext* ctx, const SphFieldColour* colour, const int32_t* lut);
+int32_t sph_field_range(SphContext* ctx, const SphFieldColour* colour, SphFieldRange* out);
+/* i32 [height, width] of the last surface frame made with a colouring: the smoothed table index of the pixel's fluid colour, -1
+ * where the pixel holds no field-coloured fluid; SPH_E_STATE if the last surface frame had none.  Synchronises. */
+int32_t sph_frame_download_field_index(SphContext* ctx, int32_t* index, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

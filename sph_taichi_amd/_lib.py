@@ -128,6 +128,20 @@ class SphSurfaceParams(C.Structure):
 SURFACE_MAX_FILTER_R, SURFACE_MAX_ITERATIONS, SURFACE_PASSES = 16, 8, 6
 SURFACE_PASS_NAMES = ("clear", "opaque_splat", "fluid_splat", "depth_smoothing", "thickness_smoothing", "shade_resolve")
 
+FIELD_MAX_OBJECTS = 32
+
+
+class SphFieldColour(C.Structure):
+    """Mirror of `struct SphFieldColour` (include/sph_hip.h); `field` is an index into render.FIELDS."""
+    _fields_ = [("field", C.c_int32), ("material", C.c_int32), ("n_objects", C.c_int32), ("object_ids", C.c_int32 * FIELD_MAX_OBJECTS),
+                ("lo", C.c_float), ("hi", C.c_float), ("axis_origin", C.c_float)]
+
+
+class SphFieldRange(C.Structure):
+    """Mirror of `struct SphFieldRange` (include/sph_hip.h)."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("count", C.c_int64), ("non_finite", C.c_int64)]
+
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -251,6 +265,9 @@ SYMBOLS = [
     ("sph_surface_download_depth", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
     ("sph_surface_download_thickness", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
     ("sph_surface_frame_timed", C.c_int32, [_ctx, C.POINTER(C.c_float), C.c_int32]),
+    ("sph_frame_set_colour", C.c_int32, [_ctx, C.POINTER(SphFieldColour), C.c_void_p]),
+    ("sph_field_range", C.c_int32, [_ctx, C.POINTER(SphFieldColour), C.POINTER(SphFieldRange)]),
+    ("sph_frame_download_field_index", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
 ]
 
 _LIB = None

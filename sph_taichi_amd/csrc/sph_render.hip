@@ -60,6 +60,21 @@
 //   px = cx + (focal * a) / zc;  py = cy - (focal * b) / zc;  skip unless 0 <= px < width and 0 <= py < height
 //   i = int(px), j = int(py);  key = bits(zc) << 32 | box rgb, box rgb[k] = uint(min(max(box_color[k], 0), 1) * 255 + 0.5)
 // Resolve: rgb = low 24 bits of the key; depth = float of the high 32 bits, +inf where they are 0xFFFFFFFF.
+//
+// Field colouring (sph_frame_set_colour; tests/fieldcolour_model.py follows it): k_frame_splat / k_frame_large<LAYER_ALL_FIELD>
+// take the place of the <LAYER_ALL> pair; a frame without a colouring launches what it always did.  A SELECTED particle
+// (material and object list of the colouring) with velocity v, position x and the record's density / pressure:
+//   s   = the field:  speed = sqrt((v.x v.x + v.y v.y) + v.z v.z);  vx, vy, vz, density, pressure: the stored value;
+//         x, y, z: x_a - axis_origin
+//   t   = (s - lo) * inv             inv = f32(1) / (f32(hi) - f32(lo)), made by the host and passed by value
+//   t   = t >= 0 ? min(t, 1) : 0     a NaN gives 0
+//   idx = int(t * 255 + 0.5)         truncation; 0 .. 255
+//   kc[k] = float(lut[idx][k]) / 255                                         lut: 256 x 3 i32 in [0, 255]
+// and the fragment is the one above.  A particle that is not selected has kc[k] = float(c[k]) / 255 as before.
+// k_field_range (sph_field_range) reduces s over the selected, visible particles whose s is finite: min and max of the
+// order-preserving u32 image of the bits of s (negative floats flipped whole, the others with the sign bit set), and the two
+// counts; wave shuffles, then LDS, then one atomicMin / atomicMax / two atomicAdd per block.  All integers: any order gives the
+// same words.  The host maps the two words back to floats.
 #include <math.h>
 
 #include "sph_render_dev.h"   // RenderCam, SphRender, the sprite / fragment / box-edge device functions (shared with sph_surface.hip)
@@ -76,24 +91,44 @@ __global__ __launch_bounds__(RTPB) void k_render_clear(unsigned long long* __res
 // does LAYER draw the particle with these flags?
 template <int LAYER>
 __device__ __forceinline__ bool frame_draws(const RenderCam& cam, int flags) {
-    if (LAYER != LAYER_ALL && sph_is_fluid(flags) != (LAYER == LAYER_FLUID)) return false;
+    if (layer_base(LAYER) != LAYER_ALL && sph_is_fluid(flags) != (layer_base(LAYER) == LAYER_FLUID)) return false;
     return render_visible(cam, flags);
 }
 
-template <int LAYER>
-__device__ __forceinline__ void frame_fragment(const RenderCam& cam, const FramePlanes& g, const Sprite& s, const float kc[3], int i, int j) {
-    if (LAYER == LAYER_FLUID) surface_fragment(cam, g.keys, g.fz, g.thick, s, i, j);
+// FIELD... = (the launch's FrameField, the particle's table index) for the *_FIELD layers, nothing for the others
+template <int LAYER, class... FIELD>
+__device__ __forceinline__ void frame_fragment(const RenderCam& cam, const FramePlanes& g, const Sprite& s, const float kc[3], int i, int j,
+                                               const FIELD&... field) {
+    if constexpr (LAYER == LAYER_FLUID) surface_fragment(cam, g.keys, g.fz, g.thick, s, i, j);
+    else if constexpr (LAYER == LAYER_FLUID_FIELD) surface_field_fragment(cam, g.keys, g.thick, s, i, j, field...);
     else render_fragment(cam, g.keys, s, kc, i, j);
 }
 
-// blocks [0, particle_blocks): one lane per particle; blocks behind them (none for LAYER_FLUID): one lane per box-edge sample
+// A *_FIELD layer's colour of particle p: its table index if it is selected (else FIELD_IDX_NONE), and, unless the layer is the
+// fluid's, kc from the table or from the object's colour.
 template <int LAYER>
+__device__ __forceinline__ int frame_colour(const FrameField& ff, const float4& x, const float4* __restrict__ aux,
+                                            const int* __restrict__ color_cold, int cold_cap, int p, float kc[3]) {
+    const float4 V = ff.vf[p], A = aux[p];
+    const bool sel = field_selected(ff.sel, __float_as_int(V.w));
+    const int idx = sel ? field_index(ff.sel, field_value(ff.sel, x, V, A)) : FIELD_IDX_NONE;
+    if (LAYER != LAYER_FLUID_FIELD) {
+        if (sel) field_lut_colour(ff.lut, idx, kc);
+        else render_colour(color_cold, __float_as_int(A.w), cold_cap, kc);
+    }
+    return idx;
+}
+
+// The two splat kernels: FIELD... = one FrameField for the *_FIELD layers; the other layers have no such argument, and their
+// arguments and their code are what they were before there was a colouring.
+// blocks [0, particle_blocks): one lane per particle; blocks behind them (none for LAYER_FLUID): one lane per box-edge sample
+template <int LAYER, class... FIELD>
 __global__ __launch_bounds__(RTPB) void k_frame_splat(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ vf,
                                                       const float4* __restrict__ aux, const int* __restrict__ color_cold, int N,
                                                       int cold_cap, int particle_blocks, FramePlanes g, int* __restrict__ big_list,
-                                                      unsigned* __restrict__ big_count, int big_cap) {
+                                                      unsigned* __restrict__ big_count, int big_cap, FIELD... field) {
     if ((int)blockIdx.x >= particle_blocks) {
-        if (LAYER != LAYER_FLUID) render_box_sample(cam, g.keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
+        if (layer_base(LAYER) != LAYER_FLUID) render_box_sample(cam, g.keys, ((int)blockIdx.x - particle_blocks) * RTPB + (int)threadIdx.x);
         return;
     }
     const int p = blockIdx.x * RTPB + threadIdx.x;
@@ -108,16 +143,22 @@ __global__ __launch_bounds__(RTPB) void k_frame_splat(RenderCam cam, const float
         return;
     }
     float kc[3] = {0.0f, 0.0f, 0.0f};
-    if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
-    for (int j = s.j0; j <= s.j1; ++j)           // at most 9 x 9: R <= SPH_RENDER_SMALL_R
-        for (int i = s.i0; i <= s.i1; ++i) frame_fragment<LAYER>(cam, g, s, kc, i, j);
+    if constexpr (layer_field(LAYER)) {
+        const int idx = frame_colour<LAYER>(field..., x, aux, color_cold, cold_cap, p, kc);
+        for (int j = s.j0; j <= s.j1; ++j)
+            for (int i = s.i0; i <= s.i1; ++i) frame_fragment<LAYER>(cam, g, s, kc, i, j, field..., idx);
+    } else {
+        if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+        for (int j = s.j0; j <= s.j1; ++j)           // at most 9 x 9: R <= SPH_RENDER_SMALL_R
+            for (int i = s.i0; i <= s.i1; ++i) frame_fragment<LAYER>(cam, g, s, kc, i, j);
+    }
 }
 
-template <int LAYER>
+template <int LAYER, class... FIELD>
 __global__ __launch_bounds__(RTPB) void k_frame_large(RenderCam cam, const float4* __restrict__ xm, const float4* __restrict__ aux,
                                                       const int* __restrict__ color_cold, int N, int cold_cap, FramePlanes g,
                                                       const int* __restrict__ big_list, const unsigned* __restrict__ big_count,
-                                                      int big_cap) {
+                                                      int big_cap, FIELD... field) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * RTPB + threadIdx.x) >> 6, n_waves = (gridDim.x * RTPB) >> 6;
     unsigned n = *big_count;
@@ -129,11 +170,19 @@ __global__ __launch_bounds__(RTPB) void k_frame_large(RenderCam cam, const float
         Sprite s;
         if (!render_sprite(cam, x.x, x.y, x.z, s)) continue;
         float kc[3] = {0.0f, 0.0f, 0.0f};
-        if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
         const int bw = s.i1 - s.i0 + 1, bh = s.j1 - s.j0 + 1;   // each <= 2 * SPH_RENDER_MAX_R + 1
-        for (int t = lane; t < bw * bh; t += 64) {
-            const int jj = t / bw;
-            frame_fragment<LAYER>(cam, g, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
+        if constexpr (layer_field(LAYER)) {
+            const int idx = frame_colour<LAYER>(field..., x, aux, color_cold, cold_cap, p, kc);
+            for (int t = lane; t < bw * bh; t += 64) {
+                const int jj = t / bw;
+                frame_fragment<LAYER>(cam, g, s, kc, s.i0 + (t - jj * bw), s.j0 + jj, field..., idx);
+            }
+        } else {
+            if (LAYER != LAYER_FLUID) render_colour(color_cold, __float_as_int(aux[p].w), cold_cap, kc);
+            for (int t = lane; t < bw * bh; t += 64) {
+                const int jj = t / bw;
+                frame_fragment<LAYER>(cam, g, s, kc, s.i0 + (t - jj * bw), s.j0 + jj);
+            }
         }
     }
 }
@@ -144,7 +193,107 @@ __global__ __launch_bounds__(RTPB) void k_render_resolve(const unsigned long lon
     if (i < n_pix) depth[i] = render_resolve_key(keys[i], rgb + 3 * (size_t)i);
 }
 
+// ---- sph_field_range ---------------------------------------------------------------------------------------------------
+#define FR_MAX_BLOCKS 256      // one block per compute unit: a block walks N / 65536 tiles and ends in four atomics
+#define FR_WAVES (RTPB / 64)
+
+// order-preserving image of f32 bits in u32 (the map of sph_columns.hip): negative values flipped whole, the others get the sign bit
+__device__ __forceinline__ unsigned field_ordered(float f) {
+    const unsigned b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+static float field_unordered(unsigned u) {
+    const unsigned b = u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu);
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+struct FieldHidden { int n; int ids[SPH_RENDER_MAX_INVISIBLE]; };   // the frames' invisible objects, by value
+
+// words: [0] ordered min, [1] ordered max, then (8-byte aligned) count and non_finite as u64
+__global__ __launch_bounds__(64) void k_field_range_clear(unsigned* __restrict__ words) {
+    if (threadIdx.x == 0) { words[0] = 0xffffffffu; words[1] = 0u; }
+    if (threadIdx.x >= 2 && threadIdx.x < 6) words[threadIdx.x] = 0u;
+}
+
+// grid = ceil(tiles / tiles_per_block) blocks of four waves; block b takes the tiles (256 records each) [b, b + 1) * tiles_per_block
+__global__ __launch_bounds__(RTPB) void k_field_range(const float4* __restrict__ xm, const float4* __restrict__ vf,
+                                                      const float4* __restrict__ aux, int N, int tiles_per_block, FieldSel sel,
+                                                      FieldHidden hidden, unsigned* __restrict__ words) {
+    __shared__ unsigned w_min[FR_WAVES], w_max[FR_WAVES];
+    __shared__ int w_count[FR_WAVES], w_bad[FR_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned lo = 0xffffffffu, hi = 0u;
+    int count = 0, bad = 0;              // per lane; a lane sees at most tiles_per_block <= 2^23 records
+    const long long first = (long long)blockIdx.x * tiles_per_block * RTPB;
+    for (int tile = 0; tile < tiles_per_block; ++tile) {
+        const long long i = first + (long long)tile * RTPB + threadIdx.x;
+        if (i >= N) break;
+        const float4 V = vf[i];
+        const int flags = __float_as_int(V.w);
+        if (!field_selected(sel, flags)) continue;
+        const int oid = sph_flags_object(flags);
+        bool visible = true;
+        for (int k = 0; k < hidden.n; ++k) visible = visible && hidden.ids[k] != oid;
+        if (!visible) continue;
+        const bool pos = sel.field >= SPH_FIELD_X, rec = sel.field == SPH_FIELD_DENSITY || sel.field == SPH_FIELD_PRESSURE;
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float s = field_value(sel, pos ? xm[i] : zero, V, rec ? aux[i] : zero);   // (only the record the field lives in is read)
+        if (isfinite(s)) {
+            const unsigned u = field_ordered(s);
+            lo = u < lo ? u : lo;
+            hi = u > hi ? u : hi;
+            ++count;
+        } else {
+            ++bad;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const unsigned ol = (unsigned)__shfl_xor((int)lo, m, 64), oh = (unsigned)__shfl_xor((int)hi, m, 64);
+        lo = ol < lo ? ol : lo;
+        hi = oh > hi ? oh : hi;
+        count += __shfl_xor(count, m, 64);
+        bad += __shfl_xor(bad, m, 64);
+    }
+    if (lane == 0) { w_min[wave] = lo; w_max[wave] = hi; w_count[wave] = count; w_bad[wave] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long n = 0, nb = 0;
+#pragma unroll
+        for (int w = 0; w < FR_WAVES; ++w) {
+            lo = w_min[w] < lo ? w_min[w] : lo;
+            hi = w_max[w] > hi ? w_max[w] : hi;
+            n += w_count[w];
+            nb += w_bad[w];
+        }
+        if (n) {
+            atomicMin(words + 0, lo);
+            atomicMax(words + 1, hi);
+            atomicAdd(reinterpret_cast<u64*>(words + 2), (u64)n);
+        }
+        if (nb) atomicAdd(reinterpret_cast<u64*>(words + 4), (u64)nb);
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------
+// the selection part of a SphFieldColour into sel; a message = what is wrong with it
+static const char* make_selection(const SphFieldColour& fc, FieldSel& sel) {
+    if (fc.field < 0 || fc.field >= SPH_FIELD_COUNT_) return "unknown field (enum SphColourField)";
+    if (fc.material < -1 || fc.material > 255) return "material must be -1 or in [0, 255]";
+    if (fc.n_objects < 0 || fc.n_objects > SPH_FIELD_MAX_OBJECTS) return "n_objects must be in [0, SPH_FIELD_MAX_OBJECTS = 32]";
+    if (!isfinite(fc.axis_origin)) return "axis_origin must be finite";
+    memset(&sel, 0, sizeof(sel));
+    sel.field = fc.field; sel.material = fc.material; sel.n_objects = fc.n_objects;
+    for (int k = 0; k < fc.n_objects; ++k) sel.object_ids[k] = fc.object_ids[k];
+    sel.origin = fc.axis_origin;
+    sel.lo = 0.0f; sel.inv = 1.0f;
+    return nullptr;
+}
+
+static bool field_needs_aux(const FieldSel& sel) { return sel.field == SPH_FIELD_DENSITY || sel.field == SPH_FIELD_PRESSURE; }
+
 static unsigned pack_unit_rgb(const float c[3]) {
     unsigned rgb = 0;
     for (int k = 0; k < 3; ++k) {
@@ -206,7 +355,7 @@ static const char* make_camera(const SphRenderParams& p, RenderCam& cam) {
     return nullptr;
 }
 
-void sph_render_release(SphContext* c) { sph_observe_release(c->render, &SphRender::block); }
+void sph_render_release(SphContext* c) { sph_observe_release(c->render, &SphRender::block, &SphRender::lut, &SphRender::range_words); }
 
 static int render_alloc(SphContext* c, SphRender* r) {
     const int W = r->cam.W, H = r->cam.H;
@@ -224,29 +373,49 @@ static int render_alloc(SphContext* c, SphRender* r) {
 }
 
 template <int LAYER>
-int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count) {
+int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count, const FrameField& field) {
     const SphLive in = sph_live(c);
     int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity; the previous layer's large launch is ahead on the stream
     const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
     const int particle_blocks = (in.N + RTPB - 1) / RTPB;
-    const int box_blocks = LAYER != LAYER_FLUID && cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
+    const int box_blocks = layer_base(LAYER) != LAYER_FLUID && cam.draw_box ? (12 * cam.S + RTPB - 1) / RTPB : 0;
+    FrameField ff = field;                    // (read by the *_FIELD layers only)
+    ff.vf = in.vf;
     if (particle_blocks + box_blocks > 0) {
-        hipLaunchKernelGGL(k_frame_splat<LAYER>, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.vf, in.aux,
-                           c->color_cold, in.N, c->cold_cap, particle_blocks, planes, big_list, big_count, big_cap);
+        if constexpr (layer_field(LAYER))
+            hipLaunchKernelGGL((k_frame_splat<LAYER, FrameField>), dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.vf,
+                               in.aux, c->color_cold, in.N, c->cold_cap, particle_blocks, planes, big_list, big_count, big_cap, ff);
+        else
+            hipLaunchKernelGGL(k_frame_splat<LAYER>, dim3(particle_blocks + box_blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.vf, in.aux,
+                               c->color_cold, in.N, c->cold_cap, particle_blocks, planes, big_list, big_count, big_cap);
         SPH_LAUNCH_CHECK(c);
     }
     if (in.N > 0) {
         int blocks = (in.N + 3) / 4;          // one wave per listed particle, at most 4096 waves striding over the list
         if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(k_frame_large<LAYER>, dim3(blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.aux, c->color_cold, in.N, c->cold_cap,
-                           planes, big_list, big_count, big_cap);
+        if constexpr (layer_field(LAYER))
+            hipLaunchKernelGGL((k_frame_large<LAYER, FrameField>), dim3(blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.aux, c->color_cold, in.N,
+                               c->cold_cap, planes, big_list, big_count, big_cap, ff);
+        else
+            hipLaunchKernelGGL(k_frame_large<LAYER>, dim3(blocks), dim3(RTPB), 0, c->stream, cam, in.xm, in.aux, c->color_cold, in.N, c->cold_cap,
+                               planes, big_list, big_count, big_cap);
         SPH_LAUNCH_CHECK(c);
     }
     return 0;
 }
-template int frame_enqueue_layer<LAYER_ALL>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
-template int frame_enqueue_layer<LAYER_OPAQUE>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
-template int frame_enqueue_layer<LAYER_FLUID>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*);
+template int frame_enqueue_layer<LAYER_ALL>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+template int frame_enqueue_layer<LAYER_OPAQUE>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+template int frame_enqueue_layer<LAYER_FLUID>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+template int frame_enqueue_layer<LAYER_ALL_FIELD>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+template int frame_enqueue_layer<LAYER_OPAQUE_FIELD>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+template int frame_enqueue_layer<LAYER_FLUID_FIELD>(SphContext*, const RenderCam&, const FramePlanes&, unsigned*, const FrameField&);
+
+// What a frame of either style does before its splats when a colouring is in force: density / pressure of a fused step live in
+// eos2 until somebody asks (as the export does).
+int frame_colour_prepare(SphContext* c, const SphRender* r) {
+    if (r->colour_on && field_needs_aux(r->sel)) return sph_ensure_aux(c);
+    return 0;
+}
 
 extern "C" {
 
@@ -276,16 +445,90 @@ int32_t sph_render_set_invisible(SphContext* c, const int32_t* object_ids, int32
     return 0;
 }
 
+int32_t sph_frame_set_colour(SphContext* c, const SphFieldColour* colour, const int32_t* lut) {
+    if (c && (colour == nullptr) != (lut == nullptr)) return sph_fail(c, SPH_E_INVALID, "sph_frame_set_colour: colour and lut are both null (off) or both given");
+    if (int rc = sph_observe_enter(c, "sph_frame_set_colour", FRAME_SLAB_WHY)) return rc;
+    if (!colour) {
+        if (c->render) c->render->colour_on = false;
+        return 0;
+    }
+    FieldSel sel;
+    if (const char* what = make_selection(*colour, sel)) {
+        snprintf(c->err, sizeof(c->err), "sph_frame_set_colour: %s", what);
+        return SPH_E_INVALID;
+    }
+    if (!isfinite(colour->lo) || !isfinite(colour->hi)) return sph_fail(c, SPH_E_INVALID, "sph_frame_set_colour: lo and hi must be finite");
+    if (!(colour->lo < colour->hi)) return sph_fail(c, SPH_E_INVALID, "sph_frame_set_colour: lo must be smaller than hi");
+    sel.lo = colour->lo;
+    sel.inv = 1.0f / (colour->hi - colour->lo);
+    if (!(sel.inv > 0.0f) || !isfinite(sel.inv)) return sph_fail(c, SPH_E_INVALID, "sph_frame_set_colour: the range is too narrow or too wide for binary32");
+    for (int k = 0; k < 256 * 3; ++k)
+        if (lut[k] < 0 || lut[k] > 255) return sph_fail(c, SPH_E_INVALID, "sph_frame_set_colour: a table entry lies outside [0, 255]");
+    SphRender* r = sph_observe_state(c->render);
+    if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_frame_set_colour: out of host memory");
+    const bool first = !r->lut;
+    if (first)
+        if (int rc = sph_observe_alloc(c, (void**)&r->lut, sizeof(r->lut_host), "sph_frame_set_colour", "the colour table")) return rc;
+    if (first || memcmp(r->lut_host, lut, sizeof(r->lut_host)) != 0) {
+        // behind the frames that still read the old table; the host copy must not change before the copy has been made
+        memcpy(r->lut_host, lut, sizeof(r->lut_host));
+        SPH_HIP(c, hipMemcpyAsync(r->lut, r->lut_host, sizeof(r->lut_host), hipMemcpyHostToDevice, c->stream));
+        SPH_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    r->sel = sel;
+    r->colour_on = true;
+    return 0;
+}
+
+int32_t sph_field_range(SphContext* c, const SphFieldColour* colour, SphFieldRange* out) {
+    if (c && (!colour || !out)) return sph_fail(c, SPH_E_INVALID, "sph_field_range: null argument");
+    if (int rc = sph_observe_enter(c, "sph_field_range", FRAME_SLAB_WHY)) return rc;
+    FieldSel sel;
+    if (const char* what = make_selection(*colour, sel)) {
+        snprintf(c->err, sizeof(c->err), "sph_field_range: %s", what);
+        return SPH_E_INVALID;
+    }
+    SphRender* r = sph_observe_state(c->render);
+    if (!r) return sph_fail(c, SPH_E_NOMEM, "sph_field_range: out of host memory");
+    if (!r->range_words)
+        if (int rc = sph_observe_alloc(c, (void**)&r->range_words, 32, "sph_field_range", "the result words")) return rc;
+    if (field_needs_aux(sel))
+        if (int rc = sph_ensure_aux(c)) return rc;
+    FieldHidden hidden;
+    hidden.n = r->cam.n_invisible;
+    memcpy(hidden.ids, r->cam.invisible, sizeof(hidden.ids));
+    const SphLive in = sph_live(c);
+    hipLaunchKernelGGL(k_field_range_clear, dim3(1), dim3(64), 0, c->stream, r->range_words);
+    SPH_LAUNCH_CHECK(c);
+    if (in.N > 0) {
+        const SphWalk w = sph_observe_walk(in.N, RTPB, FR_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_field_range, dim3(w.blocks), dim3(RTPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, sel, hidden, r->range_words);
+        SPH_LAUNCH_CHECK(c);
+    }
+    unsigned words[6];
+    if (int rc = sph_observe_download(c, words, r->range_words, sizeof(words))) return rc;
+    memcpy(&out->count, words + 2, 8);
+    memcpy(&out->non_finite, words + 4, 8);
+    out->lo = out->count > 0 ? field_unordered(words[0]) : (float)INFINITY;
+    out->hi = out->count > 0 ? field_unordered(words[1]) : -(float)INFINITY;
+    return 0;
+}
+
 int32_t sph_render_frame(SphContext* c) {
     if (int rc = sph_observe_enter(c, "sph_render_frame", FRAME_SLAB_WHY)) return rc;
     SphRender* r = c->render;
     if (!r || r->cam.W <= 0) return sph_fail(c, SPH_E_STATE, "sph_render_frame needs sph_render_set_params first");
     if (int rc = render_alloc(c, r)) return rc;
+    if (int rc = frame_colour_prepare(c, r)) return rc;
     const RenderCam& cam = r->cam;
     const int n_pix = cam.W * cam.H;     // <= 2^28
     hipLaunchKernelGGL(k_render_clear, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, cam.background, r->big_count);
     SPH_LAUNCH_CHECK(c);
-    if (int rc = frame_enqueue_layer<LAYER_ALL>(c, cam, FramePlanes{r->keys, nullptr, nullptr}, r->big_count)) return rc;
+    if (r->colour_on) {
+        if (int rc = frame_enqueue_layer<LAYER_ALL_FIELD>(c, cam, FramePlanes{r->keys, nullptr, nullptr}, r->big_count, FrameField{r->sel, r->lut, nullptr})) return rc;
+    } else {
+        if (int rc = frame_enqueue_layer<LAYER_ALL>(c, cam, FramePlanes{r->keys, nullptr, nullptr}, r->big_count)) return rc;
+    }
     hipLaunchKernelGGL(k_render_resolve, dim3((n_pix + RTPB - 1) / RTPB), dim3(RTPB), 0, c->stream, r->keys, n_pix, r->rgb, r->depth);
     SPH_LAUNCH_CHECK(c);
     r->have_frame = true;

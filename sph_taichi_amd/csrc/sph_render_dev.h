@@ -28,9 +28,30 @@ struct RenderCam {
     int draw_box;
 };
 
+// Field colouring (include/sph_hip.h, "Field colouring of the frames"; sph_render.hip states the arithmetic): which particles
+// take a table colour, from which field, and the range as lo and inv = 1 / (hi - lo).  By value into the launches, like RenderCam.
+struct FieldSel {
+    int field, material, n_objects;
+    int object_ids[SPH_FIELD_MAX_OBJECTS];
+    float lo, inv, origin;
+};
+#define FIELD_IDX_NONE 256                 // "this fluid fragment's particle is not selected" in the low half of a field-index key
+
+struct FrameField {                        // what only the *_FIELD layers read; by value
+    FieldSel sel;
+    const int* lut;                        // [256 * 3] on the device
+    unsigned long long* fzi;               // LAYER_FLUID_FIELD: per pixel min of bits(z) << 32 | index
+    const float4* vf;                      // the live velocity records (filled in by frame_enqueue_layer)
+};
+
 struct SphRender {
     SphRenderParams p;
     RenderCam cam;
+    bool colour_on;                        // sph_frame_set_colour: both frame styles colour the selected particles by sel / lut
+    FieldSel sel;
+    int* lut;                              // [256 * 3] device copy of lut_host, allocated by the first sph_frame_set_colour
+    int lut_host[256 * 3];
+    unsigned* range_words;                 // sph_field_range: ordered min, ordered max, then count and non_finite as u64 (24 B)
     int W, H;                              // what the block below is sized for
     void* block;                           // one allocation, carved into:
     unsigned long long* keys;              // [W * H]
@@ -44,7 +65,11 @@ struct Sprite { float a, b, zc, px, py, inv; int i0, i1, j0, j1; float R; };
 
 // Which particles a splat draws, and into what: every visible one or the visible ones that are not fluid as shaded spheres into
 // the min-key plane (with the box edges), or the visible fluid ones into the fluid depth / thickness planes.
-enum FrameLayer { LAYER_ALL, LAYER_OPAQUE, LAYER_FLUID };
+// The *_FIELD layers draw what their base layer draws, with the selected particles coloured by the field (FrameField): a table
+// colour instead of the object's in the min-key plane, or for the fluid the table index beside the depth in a plane of its own.
+enum FrameLayer { LAYER_ALL, LAYER_OPAQUE, LAYER_FLUID, LAYER_ALL_FIELD, LAYER_OPAQUE_FIELD, LAYER_FLUID_FIELD };
+constexpr bool layer_field(int layer) { return layer >= LAYER_ALL_FIELD; }
+constexpr int layer_base(int layer) { return layer >= LAYER_ALL_FIELD ? layer - LAYER_ALL_FIELD : layer; }
 
 struct FramePlanes {                       // by value; a layer touches only its own
     unsigned long long* keys;              // min-keys: written by LAYER_ALL / LAYER_OPAQUE, read (final by then) by LAYER_FLUID
@@ -55,7 +80,10 @@ struct FramePlanes {                       // by value; a layer touches only its
 // Enqueues one layer on the context's stream (sph_render.hip): k_frame_splat<LAYER>, then k_frame_large<LAYER> over the sprites
 // the first one listed through `big_count`, a device counter the frame's clear kernel has zeroed.
 template <int LAYER>
-int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count);
+int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count,
+                        const FrameField& field = FrameField{});
+// Before the splats of a frame of either style (sph_render.hip): materialises density / pressure if a colouring in force reads them.
+int frame_colour_prepare(SphContext* c, const SphRender* r);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ float rdot(float ax, float ay, float az, float dx, float dy, float dz) { return (ax * dx + ay * dy) + az * dz; }
@@ -127,6 +155,62 @@ __device__ __forceinline__ void surface_fragment(const RenderCam& cam, const uns
     const unsigned zb = __float_as_uint(z);
     if (zb < __hip_atomic_load(fz + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(fz + p, zb);
     if (zb < (unsigned)(keys[p] >> 32)) atomicAdd(thick + p, (unsigned)((hh / cam.radius) * 256.0f + 0.5f));   // (the opaque layer is final)
+}
+
+// the field-coloured fluid layer's fragment: surface_fragment with the depth's minimum taken together with the table index
+__device__ __forceinline__ void surface_field_fragment(const RenderCam& cam, const unsigned long long* __restrict__ keys,
+                                                       unsigned* __restrict__ thick, const Sprite& s, int i, int j,
+                                                       const FrameField& ff, int idx) {
+    unsigned long long* __restrict__ fzi = ff.fzi;
+    const float dx = (((float)i + 0.5f) - s.px) * s.inv;
+    const float dy = (s.py - ((float)j + 0.5f)) * s.inv;
+    const float h2 = (cam.r2 - dx * dx) - dy * dy;
+    if (!(h2 >= 0.0f)) return;
+    const float hh = sqrtf(h2);
+    const float z = s.zc - hh;
+    if (!(z > 0.0f)) return;
+    const size_t p = (size_t)j * cam.W + i;                    // 0 <= i < W, 0 <= j < H by the clamped box
+    const unsigned zb = __float_as_uint(z);
+    const unsigned long long key = ((unsigned long long)zb << 32) | (unsigned)idx;
+    if (key < __hip_atomic_load(fzi + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(fzi + p, key);
+    if (zb < (unsigned)(keys[p] >> 32)) atomicAdd(thick + p, (unsigned)((hh / cam.radius) * 256.0f + 0.5f));   // (the opaque layer is final)
+}
+
+// ---- field colouring: selection, field value, table index (the block "Field colouring" of sph_render.hip) ----
+__device__ __forceinline__ bool field_selected(const FieldSel& f, int flags) {
+    if (f.material >= 0 && sph_flags_material(flags) != f.material) return false;
+    if (f.n_objects > 0) {
+        const int oid = sph_flags_object(flags);
+        bool in = false;
+        for (int k = 0; k < f.n_objects; ++k) in = in || oid == f.object_ids[k];    // uniform index: scalar loads
+        return in;
+    }
+    return true;
+}
+
+__device__ __forceinline__ float field_value(const FieldSel& f, const float4& X, const float4& V, const float4& A) {
+    switch (f.field) {
+        case SPH_FIELD_SPEED: return sqrtf((V.x * V.x + V.y * V.y) + V.z * V.z);
+        case SPH_FIELD_VX: return V.x;
+        case SPH_FIELD_VY: return V.y;
+        case SPH_FIELD_VZ: return V.z;
+        case SPH_FIELD_DENSITY: return A.y;
+        case SPH_FIELD_PRESSURE: return A.z;
+        case SPH_FIELD_X: return X.x - f.origin;
+        case SPH_FIELD_Y: return X.y - f.origin;
+        default: return X.z - f.origin;
+    }
+}
+
+__device__ __forceinline__ int field_index(const FieldSel& f, float s) {
+    float t = (s - f.lo) * f.inv;
+    t = t >= 0.0f ? fminf(t, 1.0f) : 0.0f;                     // (a NaN compares false: 0)
+    return (int)(t * 255.0f + 0.5f);                           // 0 .. 255
+}
+
+__device__ __forceinline__ void field_lut_colour(const int* __restrict__ lut, int idx, float kc[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) kc[k] = (float)lut[3 * idx + k] / 255.0f;
 }
 
 // a resolved min-key: its colour bytes into rgb[0 .. 2]; returns its depth, +inf where nothing was drawn

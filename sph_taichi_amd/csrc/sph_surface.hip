@@ -80,6 +80,26 @@
 //     col = ((T * behind[k] + (1 - T) * (fluid_color[k] * lit)) * (1 - F) + F * sky[k]) + spec
 //     byte k = uint(min(max(col, 0), 1) * 255 + 0.5)                                 truncation; a NaN col gives 0
 //   depth = z;  thickness = t.
+//
+// ---- WITH A FIELD COLOURING (sph_frame_set_colour; tests/fieldcolour_model.py follows this block) ------------------
+// A frame without one runs none of what follows and allocates none of its planes.  idx of a particle, lut and SELECTED are those
+// of the block "Field colouring" in sph_render.hip.
+// Opaque layer: if the colouring's material is not fluid, its selected particles take kc[k] = float(lut[idx][k]) / 255 there
+//   (k_frame_splat / k_frame_large<LAYER_OPAQUE_FIELD>); else the layer is the one above.
+// Fluid layer: if the colouring's material is fluid or any, k_frame_splat / k_frame_large<LAYER_FLUID_FIELD> take the place of
+//   the <LAYER_FLUID> pair (else the fluid is drawn as above).  A fluid fragment (the same sphere, the same skips), with
+//   e = idx if its particle is selected, else 256:
+//     Q = min(Q, bits(z) << 32 | e)                                                 u64, starts at 0xFFFFFFFF'FFFFFFFF
+//     S as above.
+//   D := the high 32 bits of Q (k_surface_field_split); depth and thickness smoothing read it as above.  The low 32 bits are
+//   the e of the pixel's nearest fluid fragment, the smaller e among fragments of equal depth: a function of the set.
+// A pixel HAS AN INDEX iff it has fluid and its e is not 256; then v0 = float(e).
+// Index smoothing (k_surface_smooth_index), one pass; a pixel p without an index gets I[p] = -1; else
+//   R = R(z0[p]), R2 as above;  sw = 0;  sv = 0
+//   for dj, di as above over the q inside the image that have an index:  s2, ws as in the thickness pass;
+//     sw = sw + ws;  sv = sv + ws * v0[q]
+//   v = sv / sw;  I[p] = int(min(max(v + 0.5, 0), 255))                              truncation (the centre tap has ws = 1: sw >= 1)
+// Shade: in col, fluid_color[k] is replaced by float(lut[I[p]][k]) / 255 where I[p] >= 0; everything else is unchanged.
 #include <math.h>
 
 #include "sph_render_dev.h"
@@ -112,6 +132,12 @@ struct SphSurface {
     unsigned char* rgb;               // [3 n] output
     unsigned* counts;                 // [2] large-sprite counters: opaque, fluid
     bool have_frame;
+    // only for frames with a field colouring: a second allocation, made by the first such frame
+    int fW, fH;                       // what it is sized for
+    void* fblock;                     // carved into:
+    unsigned long long* fzi;          // [n] min of bits(z) << 32 | index over the fluid fragments
+    int* fidx;                        // [n] smoothed table index, -1 where the pixel has none
+    bool have_index;                  // the last frame wrote fidx
 };
 
 __device__ __forceinline__ float surf_depth(unsigned bits) { return __uint_as_float(bits == SURF_NONE ? SURF_INF_BITS : bits); }
@@ -216,10 +242,20 @@ __device__ __forceinline__ V3 surf_point(const RenderCam& cam, int i, int j, flo
 }
 __device__ __forceinline__ V3 sub3(const V3& p, const V3& q) { return V3{p.x - q.x, p.y - q.y, p.z - q.z}; }
 
+// the fluid's body colour of pixel pix, channel k: the style's, or with a field colouring (the two extra kernel arguments) the
+// table's where the pixel has an index
+__device__ __forceinline__ float surf_body(const SurfK& sk, int, int k) { return sk.fluid[k]; }
+__device__ __forceinline__ float surf_body(const SurfK& sk, int pix, int k, const int* __restrict__ fidx, const int* __restrict__ lut) {
+    const int fi = fidx[pix];                                  // -1 or 0 .. 255
+    return fi >= 0 ? (float)lut[3 * fi + k] / 255.0f : sk.fluid[k];
+}
+
+// FIELD... = nothing: the frame without a colouring, with the arguments and the code it always had; = (fidx, lut): with one
+template <class... FIELD>
 __global__ __launch_bounds__(RTPB) void k_surface_resolve(RenderCam cam, SurfK sk, const unsigned long long* __restrict__ keys,
                                                           const unsigned* __restrict__ zs, const float* __restrict__ ts,
                                                           unsigned char* __restrict__ rgb, float* __restrict__ depth,
-                                                          float* __restrict__ thickness) {
+                                                          float* __restrict__ thickness, FIELD... field) {
     const int pix = blockIdx.x * RTPB + threadIdx.x;
     if (pix >= cam.W * cam.H) return;
     const int j = pix / cam.W, i = pix - j * cam.W;
@@ -279,15 +315,78 @@ __global__ __launch_bounds__(RTPB) void k_surface_resolve(RenderCam cam, SurfK s
         const float behind = (float)((lo >> (16 - 8 * k)) & 255u) / 255.0f;
         const float ak = 1.0f + sk.absorb[k] * t;
         const float T = 1.0f / (ak * ak);
-        const float col = ((T * behind + (1.0f - T) * (sk.fluid[k] * lit)) * (1.0f - F) + F * sk.sky[k]) + spec;
+        const float col = ((T * behind + (1.0f - T) * (surf_body(sk, pix, k, field...) * lit)) * (1.0f - F) + F * sk.sky[k]) + spec;
         rgb[3 * (size_t)pix + k] = (unsigned char)(unsigned)(fminf(fmaxf(col, 0.0f), 1.0f) * 255.0f + 0.5f);
     }
     depth[pix] = z;
     thickness[pix] = t;
 }
 
+// ---- with a field colouring --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RTPB) void k_surface_field_clear(unsigned long long* __restrict__ fzi, int n_pix) {
+    const int i = blockIdx.x * RTPB + threadIdx.x;
+    if (i < n_pix) fzi[i] = 0xFFFFFFFFFFFFFFFFull;
+}
+
+// the fluid depth plane the filters read = the high half of the index keys
+__global__ __launch_bounds__(RTPB) void k_surface_field_split(const unsigned long long* __restrict__ fzi, unsigned* __restrict__ fz, int n_pix) {
+    const int i = blockIdx.x * RTPB + threadIdx.x;
+    if (i < n_pix) fz[i] = (unsigned)(fzi[i] >> 32);
+}
+
+// The tiling of k_surface_smooth_thick over the table indices; a staged value < 0 means "no index there".
+__global__ __launch_bounds__(STILE * STILE) void k_surface_smooth_index(int W, int H, float fw, const unsigned long long* __restrict__ fzi,
+                                                                        int* __restrict__ fidx) {
+    __shared__ float tile[SLDS][SLDS];
+    const int tx = threadIdx.x & (STILE - 1), ty = threadIdx.x >> 4;
+    const int bi = blockIdx.x * STILE, bj = blockIdx.y * STILE;
+    for (int t = threadIdx.x; t < SLDS * SLDS; t += STILE * STILE) {
+        const int ly = t / SLDS, lx = t - ly * SLDS;
+        const int gi = bi - SHALO + lx, gj = bj - SHALO + ly;
+        float v = -1.0f;
+        if (gi >= 0 && gi < W && gj >= 0 && gj < H) {
+            const unsigned long long q = fzi[(size_t)gj * W + gi];
+            const unsigned e = (unsigned)q;
+            if ((unsigned)(q >> 32) != SURF_NONE && e < (unsigned)FIELD_IDX_NONE) v = (float)e;
+        }
+        tile[ly][lx] = v;
+    }
+    __syncthreads();
+    const int i = bi + tx, j = bj + ty;
+    if (i >= W || j >= H) return;
+    const size_t p = (size_t)j * W + i;
+    const unsigned zb = (unsigned)(fzi[p] >> 32);
+    if (tile[ty + SHALO][tx + SHALO] < 0.0f) { fidx[p] = -1; return; }
+    const int R = surf_radius(fw, __uint_as_float(zb));        // 1 .. SHALO: every tap below lies inside the staged window
+    const float R2 = (float)(R * R);
+    float sw = 0.0f, sv = 0.0f;
+    for (int dj = -R; dj <= R; ++dj)
+        for (int di = -R; di <= R; ++di) {
+            const float vq = tile[ty + SHALO + dj][tx + SHALO + di];
+            if (vq < 0.0f) continue;
+            const float s2 = (float)(di * di + dj * dj) / R2;
+            if (!(s2 < 1.0f)) continue;
+            const float ws = (1.0f - s2) * (1.0f - s2);
+            sw = sw + ws;
+            sv = sv + ws * vq;
+        }
+    fidx[p] = (int)fminf(fmaxf(sv / sw + 0.5f, 0.0f), 255.0f);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------
-void sph_surface_release(SphContext* c) { sph_observe_release(c->surface, &SphSurface::block); }
+void sph_surface_release(SphContext* c) { sph_observe_release(c->surface, &SphSurface::block, &SphSurface::fblock); }
+
+// the planes of a frame with a field colouring (12 bytes per pixel)
+static int surface_field_alloc(SphContext* c, SphSurface* s, int W, int H) {
+    if (s->fblock && s->fW == W && s->fH == H) return 0;
+    s->fW = s->fH = 0; s->have_index = false;
+    const size_t n = (size_t)W * H;        // n <= 2^28
+    if (int rc = sph_observe_alloc(c, &s->fblock, 12 * n, "sph_surface_frame", "the field-index planes")) return rc;
+    s->fzi = (unsigned long long*)s->fblock;
+    s->fidx = (int*)((char*)s->fblock + 8 * n);
+    s->fW = W; s->fH = H;
+    return 0;
+}
 
 static int surface_alloc(SphContext* c, SphSurface* s, int W, int H) {
     if (s->block && s->W == W && s->H == H) return 0;
@@ -332,6 +431,14 @@ static int surface_frame(SphContext* c, hipEvent_t* ev) {
     if (!s || !s->have_params) return sph_fail(c, SPH_E_STATE, "sph_surface_frame needs sph_surface_set_params first");
     const RenderCam& cam = r->cam;
     if (int rc = surface_alloc(c, s, cam.W, cam.H)) return rc;
+    // a field colouring: which of the two layers holds selected particles (a material other than fluid: only the opaque one)
+    const bool opaque_field = r->colour_on && r->sel.material != SPH_MATERIAL_FLUID;
+    const bool fluid_field = r->colour_on && (r->sel.material < 0 || r->sel.material == SPH_MATERIAL_FLUID);
+    if (fluid_field)
+        if (int rc = surface_field_alloc(c, s, cam.W, cam.H)) return rc;
+    if (int rc = frame_colour_prepare(c, r)) return rc;
+    const FrameField field{r->sel, r->lut, fluid_field ? s->fzi : nullptr};
+    s->have_index = false;
     SurfK sk;
     sk.fw = s->p.filter_radius * cam.focal;
     sk.depth_range = s->p.depth_range;
@@ -346,10 +453,24 @@ static int surface_frame(SphContext* c, hipEvent_t* ev) {
     SURF_MARK();
     hipLaunchKernelGGL(k_surface_clear, dim3(pix_blocks), dim3(RTPB), 0, c->stream, s->keys, s->fz, s->thick, n_pix, cam.background, s->counts);
     SPH_LAUNCH_CHECK(c);
+    if (fluid_field) {
+        hipLaunchKernelGGL(k_surface_field_clear, dim3(pix_blocks), dim3(RTPB), 0, c->stream, s->fzi, n_pix);
+        SPH_LAUNCH_CHECK(c);
+    }
     SURF_MARK();
-    if (int rc = frame_enqueue_layer<LAYER_OPAQUE>(c, cam, planes, s->counts + 0)) return rc;
+    if (opaque_field) {
+        if (int rc = frame_enqueue_layer<LAYER_OPAQUE_FIELD>(c, cam, planes, s->counts + 0, field)) return rc;
+    } else {
+        if (int rc = frame_enqueue_layer<LAYER_OPAQUE>(c, cam, planes, s->counts + 0)) return rc;
+    }
     SURF_MARK();
-    if (int rc = frame_enqueue_layer<LAYER_FLUID>(c, cam, planes, s->counts + 1)) return rc;
+    if (fluid_field) {
+        if (int rc = frame_enqueue_layer<LAYER_FLUID_FIELD>(c, cam, planes, s->counts + 1, field)) return rc;
+        hipLaunchKernelGGL(k_surface_field_split, dim3(pix_blocks), dim3(RTPB), 0, c->stream, s->fzi, s->fz, n_pix);
+        SPH_LAUNCH_CHECK(c);
+    } else {
+        if (int rc = frame_enqueue_layer<LAYER_FLUID>(c, cam, planes, s->counts + 1)) return rc;
+    }
     SURF_MARK();
     const dim3 tiles((cam.W + STILE - 1) / STILE, (cam.H + STILE - 1) / STILE);
     const unsigned* zs = s->fz;
@@ -362,12 +483,21 @@ static int surface_frame(SphContext* c, hipEvent_t* ev) {
     SURF_MARK();
     hipLaunchKernelGGL(k_surface_smooth_thick, tiles, dim3(STILE * STILE), 0, c->stream, cam.W, cam.H, sk.fw, sk.tk, s->fz, s->thick, s->ts);
     SPH_LAUNCH_CHECK(c);
+    if (fluid_field) {
+        hipLaunchKernelGGL(k_surface_smooth_index, tiles, dim3(STILE * STILE), 0, c->stream, cam.W, cam.H, sk.fw, s->fzi, s->fidx);
+        SPH_LAUNCH_CHECK(c);
+    }
     SURF_MARK();
-    hipLaunchKernelGGL(k_surface_resolve, dim3(pix_blocks), dim3(RTPB), 0, c->stream, cam, sk, s->keys, zs, s->ts, s->rgb, s->depth, s->thickness);
+    if (fluid_field)
+        hipLaunchKernelGGL((k_surface_resolve<const int*, const int*>), dim3(pix_blocks), dim3(RTPB), 0, c->stream, cam, sk, s->keys, zs, s->ts,
+                           s->rgb, s->depth, s->thickness, (const int*)s->fidx, (const int*)r->lut);
+    else
+        hipLaunchKernelGGL(k_surface_resolve<>, dim3(pix_blocks), dim3(RTPB), 0, c->stream, cam, sk, s->keys, zs, s->ts, s->rgb, s->depth, s->thickness);
     SPH_LAUNCH_CHECK(c);
     SURF_MARK();
 #undef SURF_MARK
     s->have_frame = true;
+    s->have_index = fluid_field;
     return 0;
 }
 
@@ -420,5 +550,15 @@ int32_t sph_surface_download(SphContext* c, uint8_t* rgb, size_t bytes) { return
 int32_t sph_surface_download_depth(SphContext* c, float* depth, size_t bytes) { return surface_download(c, depth, bytes, 1); }
 
 int32_t sph_surface_download_thickness(SphContext* c, float* thickness, size_t bytes) { return surface_download(c, thickness, bytes, 2); }
+
+int32_t sph_frame_download_field_index(SphContext* c, int32_t* index, size_t bytes) {
+    if (!c) return SPH_E_INVALID;
+    SphSurface* s = c->surface;
+    if (!s || !s->have_frame || !s->have_index)
+        return sph_fail(c, SPH_E_STATE, "sph_frame_download_field_index: the last surface frame (if any) coloured no fluid by a field");
+    if (!index || bytes != (size_t)s->W * s->H * 4)
+        return sph_fail(c, SPH_E_INVALID, "sph_frame_download_field_index: size mismatch (i32 [H, W] of the last surface frame)");
+    return sph_observe_download(c, index, s->fidx, bytes);
+}
 
 }  // extern "C"

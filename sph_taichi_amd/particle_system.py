@@ -500,12 +500,54 @@ class ParticleSystem:
         self._call(symbol, out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
-    def render(self, camera=None, invisible_objects=(), size=(1024, 1024)) -> np.ndarray:
+    def field_range(self, field, material="fluid", objects=None, invisible_objects=()):
+        """(lo, hi, count, non_finite) of `field` (render.FIELDS; a position is taken as it is) over the particles that `material`
+        and `objects` select as a `render.FieldColour` does and that are not of an invisible object: minimum and maximum of the
+        finite values, their number, and the number of values that are not finite.  Over no particle: (inf, -inf, 0, n).  One
+        streaming pass on the device behind whatever was enqueued; 24 bytes are copied back (synchronises).  Exact for any
+        particle order."""
+        from . import render as _render
+        return self._field_range(_render.FieldColour(field, material=material, objects=objects), invisible_objects)
+
+    def _field_range(self, colour, invisible_objects):
+        from . import render as _render
+        ids = [int(i) for i in invisible_objects]
+        self._call("sph_render_set_invisible", (C.c_int32 * max(len(ids), 1))(*ids), len(ids))
+        fp, out = _render.field_colour_params(colour), _lib.SphFieldRange()
+        self._call("sph_field_range", C.byref(fp), C.byref(out))
+        return float(out.lo), float(out.hi), int(out.count), int(out.non_finite)
+
+    def _set_colour(self, colour, invisible_objects):
+        """The colouring of the next frame, of either style: None switches it off (a context that never had one is not
+        touched); else the range is the colouring's or, reduced on the device, that of the particles it colours.  The range in
+        force is kept in `frame_colour_range`."""
+        from . import render as _render
+        if colour is None:
+            if getattr(self, "_colour_on", False):
+                self._call("sph_frame_set_colour", None, None)
+                self._colour_on = False
+            self.frame_colour_range = None
+            return
+        if not isinstance(colour, _render.FieldColour):
+            raise TypeError("colour must be a render.FieldColour or None")
+        rng = colour.range
+        if rng is None:
+            lo, hi, count, _ = ParticleSystem._field_range(self, colour, invisible_objects)
+            rng = _render.auto_range(lo, hi, count)
+        fp = _render.field_colour_params(colour, rng)
+        lut = colour.lut()
+        self._call("sph_frame_set_colour", C.byref(fp), lut.ctypes.data_as(C.c_void_p))
+        self._colour_on = True
+        self.frame_colour_range = (float(np.float32(rng[0])), float(np.float32(rng[1])))
+
+    def render(self, camera=None, invisible_objects=(), size=(1024, 1024), colour=None) -> np.ndarray:
         """The particles as lit spheres of radius `particle_radius` in their objects' colours plus the domain box, seen
         from `camera` (default: the reference's window camera), as uint8 [H, W, 3] with row 0 at the top; `size` =
-        (width, height).  Rendered on the GPU behind whatever was enqueued before; only the image is copied back.
-        Independent of `GGUI` and of `copy_to_vis_buffer`."""
+        (width, height).  `colour`: a `render.FieldColour` -- the particles it selects are coloured by a field (speed, density,
+        pressure, height ...) through a colour table instead; None: every particle in its object's colour.  Rendered on the GPU
+        behind whatever was enqueued before; only the image is copied back.  Independent of `GGUI` and of `copy_to_vis_buffer`."""
         shape = ParticleSystem._set_view(self, camera, invisible_objects, size)   # (by class: stand-ins borrow this method alone)
+        ParticleSystem._set_colour(self, colour, invisible_objects)
         self._call("sph_render_frame")
         self._render_shape = shape
         out = np.empty(shape + (3,), dtype=np.uint8)
@@ -522,15 +564,19 @@ class ParticleSystem:
         blocks = self.cfg.get_fluid_blocks()
         return tuple(blocks[0].get("color", (50, 100, 200))) if blocks else (50, 100, 200)
 
-    def render_surface(self, camera=None, invisible_objects=(), size=(1024, 1024), style=None) -> np.ndarray:
+    def render_surface(self, camera=None, invisible_objects=(), size=(1024, 1024), style=None, colour=None) -> np.ndarray:
         """The fluid as ONE shaded surface -- screen-space depth and thickness, the depth smoothed in image space, normals
         from it, absorption by thickness, Fresnel and a highlight -- over the solids and the domain box drawn as `render`
         draws them; uint8 [H, W, 3] with row 0 at the top.  `style`: a `render.SurfaceStyle` (None: its defaults, with the
-        filter radius 3 x and the depth range 4 x the particle radius and the first fluid block's colour).  Rendered on the
-        GPU behind whatever was enqueued before; only the image is copied back.  Reads the particles; changes nothing."""
+        filter radius 3 x and the depth range 4 x the particle radius and the first fluid block's colour).  `colour`: a
+        `render.FieldColour` -- the surface's body colour comes from the field at the visible surface (the table index of each
+        pixel's nearest selected fluid particle, smoothed like the thickness), selected solids are coloured as `render` colours
+        them; None: the style's fluid colour.  Rendered on the GPU behind whatever was enqueued before; only the image is copied
+        back.  Reads the particles; changes nothing."""
         from . import render as _render
         shape = ParticleSystem._set_view(self, camera, invisible_objects, size)   # (by class: stand-ins borrow this method alone)
-        sp = _render.surface_params(_render.resolve_style(style, self.particle_radius, self._first_fluid_colour()))
+        ParticleSystem._set_colour(self, colour, invisible_objects)
+        sp =_render.surface_params(_render.resolve_style(style, self.particle_radius, self._first_fluid_colour()))
         self._call("sph_surface_set_params", C.byref(sp))
         self._call("sph_surface_frame")
         self._surface_shape = shape
@@ -550,6 +596,16 @@ class ParticleSystem:
         """float32 [H, W] of the last `render_surface`: the smoothed thickness of the fluid in front of the solids along
         each pixel's ray, in world units; 0 where no fluid is shown."""
         return self._surface_plane("sph_surface_download_thickness", "render_surface_thickness")
+
+    def render_surface_field_index(self) -> np.ndarray:
+        """int32 [H, W] of the last `render_surface` made with a `colour` that selects fluid: the smoothed colour-table index
+        of each pixel's fluid, -1 where the pixel holds no field-coloured fluid."""
+        shape = getattr(self, "_surface_shape", None)
+        if shape is None:
+            raise _lib.SphError("render_surface_field_index: no surface frame has been rendered")
+        out = np.empty(shape, dtype=np.int32)
+        self._call("sph_frame_download_field_index", out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
 
     def copy_to_vis_buffer(self, invisible_objects=[]):
         """particle_system.py:392-407 (host copy; there is no GGUI here)."""

@@ -129,20 +129,172 @@ def surface_params(style: SurfaceStyle) -> "_lib.SphSurfaceParams":
     return p
 
 
+# ---- field colouring of the frames (csrc/sph_render.hip states the index arithmetic) ----
+# enum SphColourField, in its order
+FIELDS = ("speed", "vx", "vy", "vz", "density", "pressure", "x", "y", "z")
+_MATERIALS = {"fluid": 1, "solid": 0}          # particle_system.py:30-31 of the reference
+# Control points (position in [0, 1], red, green, blue) of the built-in maps; colormap() interpolates between them.
+_COLORMAPS = {
+    "heat": ((0.0, 0, 0, 0), (0.3, 160, 0, 0), (0.55, 255, 70, 0), (0.8, 255, 210, 0), (1.0, 255, 255, 255)),
+    "coolwarm": ((0.0, 59, 76, 192), (0.25, 141, 176, 254), (0.5, 221, 221, 221), (0.75, 244, 154, 123), (1.0, 180, 4, 38)),
+    "grey": ((0.0, 0, 0, 0), (1.0, 255, 255, 255)),
+    "rainbow": ((0.0, 0, 0, 255), (0.25, 0, 255, 255), (0.5, 0, 255, 0), (0.75, 255, 255, 0), (1.0, 255, 0, 0)),
+}
+
+
+def colormap(name: str) -> np.ndarray:
+    """uint8 [256, 3] of a built-in map: entry i is the map at i / 255, each channel interpolated linearly between the control
+    points in float64 and rounded (half up)."""
+    if not isinstance(name, str) or name not in _COLORMAPS:
+        raise ValueError(f"colormap must be one of {', '.join(sorted(_COLORMAPS))} or a uint8 [256, 3] array, not {name!r}")
+    pts = np.array(_COLORMAPS[name], dtype=np.float64)
+    t = np.arange(256, dtype=np.float64) / 255.0
+    cols = [np.interp(t, pts[:, 0], pts[:, 1 + k]) for k in range(3)]
+    return np.floor(np.stack(cols, axis=-1) + 0.5).astype(np.uint8)
+
+
+@dataclass
+class FieldColour:
+    """Colour the selected particles of a frame by a field instead of by their object (`ParticleSystem.render(colour=...)`,
+    `render_surface(colour=...)`).  `field`: one of FIELDS -- velocity magnitude or a component, density, pressure, or the position
+    along an axis minus `axis_origin`.  `range` = (lo, hi): the field values of the first and the last table entry; None: minimum
+    and maximum over the particles that are coloured, reduced on the device before the frame (an empty or degenerate one becomes
+    (lo, lo + 1)).  `colormap`: a built-in name or a uint8 [256, 3] array.  `material` ("fluid", "solid" or None) and `objects` (ids,
+    None: all) choose the particles that take the field colour; the others keep their object colour."""
+    field: str
+    range: tuple | None = None
+    colormap: object = "heat"
+    material: str | None = "fluid"
+    objects: list | None = None
+    axis_origin: float = 0.0
+
+    def __post_init__(self):
+        if not isinstance(self.field, str) or self.field not in FIELDS:
+            raise ValueError(f"field must be one of {', '.join(FIELDS)}, not {self.field!r}")
+        if self.range is not None:
+            self.range = check_range(self.range)
+        if self.material is not None and self.material not in _MATERIALS:
+            raise ValueError(f"material must be \"fluid\", \"solid\" or None, not {self.material!r}")
+        if self.objects is not None:
+            ids = [self.objects] if isinstance(self.objects, (int, np.integer)) else list(self.objects)
+            if any(isinstance(o, bool) or not isinstance(o, (int, np.integer)) or o < 0 for o in ids):
+                raise ValueError("objects must be a list of object ids (integers >= 0) or None")
+            if not ids or len(ids) > _lib.FIELD_MAX_OBJECTS:
+                raise ValueError(f"objects holds {len(ids)} ids: pass None for every object, at most {_lib.FIELD_MAX_OBJECTS} otherwise")
+            self.objects = [int(o) for o in ids]
+        self.axis_origin = float(self.axis_origin)
+        if not math.isfinite(self.axis_origin):
+            raise ValueError("axis_origin must be finite")
+        self.lut()
+
+    def lut(self) -> np.ndarray:
+        """The table as int32 [256, 3] (what the library takes)."""
+        if isinstance(self.colormap, str):
+            return colormap(self.colormap).astype(np.int32)
+        a = np.asarray(self.colormap)
+        if a.dtype != np.uint8 or a.shape != (256, 3):
+            raise ValueError(f"colormap must be one of {', '.join(sorted(_COLORMAPS))} or a uint8 [256, 3] array, "
+                             f"not {a.dtype} {list(a.shape)}")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def colormap_name(self) -> str:
+        return self.colormap if isinstance(self.colormap, str) else "custom"
+
+
+def check_range(rng) -> tuple:
+    """(lo, hi) as floats; ValueError unless both are finite, lo < hi in binary32 and 1 / (hi - lo) is a finite binary32."""
+    try:
+        lo, hi = (float(v) for v in rng)
+    except (TypeError, ValueError):
+        raise ValueError(f"range must be (lo, hi) or None, not {rng!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"range must be finite, not ({lo}, {hi})")
+    with np.errstate(all="ignore"):
+        width = np.float32(hi) - np.float32(lo)
+        inv = np.float32(1) / width if width > 0 else np.float32(0)
+    if not lo < hi or not width > 0:
+        raise ValueError(f"range needs lo < hi (in binary32), not ({lo}, {hi})")
+    if not (np.isfinite(inv) and inv > 0):
+        raise ValueError(f"range ({lo}, {hi}) is too narrow or too wide for binary32")
+    return (lo, hi)
+
+
+def auto_range(lo: float, hi: float, count: int) -> tuple:
+    """The range of a frame whose FieldColour has none, from a device reduction: (0, 1) over no particle, (lo, lo + 1) where
+    (lo, hi) is not a usable range."""
+    if count <= 0:
+        return (0.0, 1.0)
+    try:
+        return check_range((lo, hi))
+    except ValueError:
+        return (float(lo), float(np.float32(lo) + np.float32(1)))
+
+
+_COLOUR_KEYS = {"field": "field", "range": "range", "colormap": "colormap", "material": "material", "objects": "objects",
+                "axisOrigin": "axis_origin"}
+
+
+def field_colour_from_config(entry) -> FieldColour | None:
+    """The scene file's "frameColour": {"field": "speed", "range": [0, 3], "colormap": "heat", "material": "fluid", "objects": [0],
+    "axisOrigin": 0} (every key but "field" optional), or just the field's name; None = no colouring.  A colormap is given by name."""
+    if entry is None:
+        return None
+    if isinstance(entry, str):
+        entry = {"field": entry}
+    if not isinstance(entry, dict):
+        raise ValueError(f"frameColour must be an object with a \"field\" key or a field name, not {entry!r}")
+    kw = {}
+    for key, val in entry.items():
+        if key not in _COLOUR_KEYS:
+            raise ValueError(f"frameColour: unknown key {key!r} (known: {', '.join(sorted(_COLOUR_KEYS))})")
+        kw[_COLOUR_KEYS[key]] = val
+    if "field" not in kw:
+        raise ValueError(f"frameColour needs a \"field\" key: one of {', '.join(FIELDS)}")
+    if "colormap" in kw and not isinstance(kw["colormap"], str):
+        raise ValueError(f"frameColour: colormap must be one of {', '.join(sorted(_COLORMAPS))}")
+    try:
+        return FieldColour(**kw)
+    except ValueError as e:
+        raise ValueError(f"frameColour: {e}") from None
+
+
+def field_colour_params(colour: FieldColour, rng=(0.0, 1.0)) -> "_lib.SphFieldColour":
+    """The C struct for `colour` with the range `rng`."""
+    p = _lib.SphFieldColour()
+    p.field = FIELDS.index(colour.field)
+    p.material = -1 if colour.material is None else _MATERIALS[colour.material]
+    ids = colour.objects or []
+    p.n_objects = len(ids)
+    for k, oid in enumerate(ids):
+        p.object_ids[k] = oid
+    p.lo, p.hi = float(rng[0]), float(rng[1])
+    p.axis_origin = colour.axis_origin
+    return p
+
+
 def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def write_png(path: str, rgb: np.ndarray, level: int = 6):
-    """8-bit RGB PNG of a uint8 [H, W, 3] array (row 0 at the top): IHDR, one IDAT (filter 0 on every row), IEND."""
+def write_png(path: str, rgb: np.ndarray, level: int = 6, text=None):
+    """8-bit RGB PNG of a uint8 [H, W, 3] array (row 0 at the top): IHDR, one IDAT (filter 0 on every row), IEND.  `text`: a dict
+    written as tEXt chunks (keyword, Latin-1 text) between IHDR and IDAT, in the dict's order; None: no such chunk."""
     a = np.ascontiguousarray(rgb)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError("write_png: expected uint8 [H, W, 3]")
+    chunks = []
+    for key, val in (text or {}).items():
+        k, v = str(key).encode("latin-1"), str(val).encode("latin-1")
+        if not 1 <= len(k) <= 79 or b"\0" in k or b"\0" in v:
+            raise ValueError(f"write_png: a tEXt keyword has 1 to 79 Latin-1 characters and no NUL, not {key!r}")
+        chunks.append(_chunk(b"tEXt", k + b"\0" + v))
     h, w = a.shape[:2]
     rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)         # a filter-type byte in front of every row
     rows[:, 1:] = a.reshape(h, 3 * w)
     with open(path, "wb") as fh:
         fh.write(b"\x89PNG\r\n\x1a\n")
         fh.write(_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))
+        for c in chunks:
+            fh.write(c)
         fh.write(_chunk(b"IDAT", zlib.compress(rows.tobytes(), level)))
         fh.write(_chunk(b"IEND", b""))

@@ -29,6 +29,10 @@ packed on the device (export.py), so vertex k is the same particle in every file
 (ParticleSystem.render_surface: the fluid as one shaded surface over the solids) instead of the reference's spheres; an optional
 "surfaceStyle": {"iterations", "filterRadius", "depthRange", "fluidColor", "absorb", "sky", "f0", "specular"} overrides the
 defaults of render.SurfaceStyle.  Absent or "spheres": the frames are what they were.
+`"frameColour": {"field": "speed", "range": [0, 3], "colormap": "heat", "material": "fluid", "objects": [0], "axisOrigin": 0}` (only
+"field" is needed; `--frame_colour FIELD` is the short form) colours the selected particles of either frame style by a field
+(render.FieldColour); without "range" each frame takes the range of its own particles, reduced on the device.  Each PNG then
+carries field, lo, hi and colormap as tEXt chunks, and the final report holds `frame_colour_range`, the range of the last frame.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -77,6 +81,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--frame_style", choices=["spheres", "surface"], default=None,
                     help="style of the exportFrame images: every particle a sphere (the reference's window), or the fluid as one "
                          "shaded surface over the solids (default: the scene's \"frameStyle\", else spheres)")
+    ap.add_argument("--frame_colour", default=None, metavar="FIELD",
+                    help="colour the fluid of the exportFrame images by a field (speed, vx, vy, vz, density, pressure, x, y, z) over its "
+                         "range in each frame; short for the scene's \"frameColour\": {\"field\": FIELD}, which it overrides")
     return ap
 
 
@@ -103,6 +110,9 @@ def main(argv=None):
     frame_style = args.frame_style or config.get_cfg("frameStyle") or "spheres"
     if frame_style not in ("spheres", "surface"):
         raise ValueError(f"frameStyle must be \"spheres\" or \"surface\", not {frame_style!r}")
+    from .render import field_colour_from_config
+    frame_colour = field_colour_from_config(args.frame_colour if args.frame_colour is not None else config.get_cfg("frameColour"))
+    frame_colour_range = None
     if output_frames:
         from .render import Camera, surface_style_from_config, write_png
         if frame_style == "surface":
@@ -156,13 +166,20 @@ def main(argv=None):
         if output_frames and cnt % output_interval == 0:
             ps.sync()                          # the frame's cost, not the steps still in flight before it
             tr = time.perf_counter()
+            coloured = {"colour": frame_colour} if frame_colour is not None else {}     # (without the key: the calls as they were)
             if surface_style is not None:
                 img = ps.render_surface(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size),
-                                        style=surface_style)
+                                        style=surface_style, **coloured)
             else:
-                img = ps.render(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size))
+                img = ps.render(camera=camera, invisible_objects=invisible_objects, size=tuple(args.image_size), **coloured)
             render_s += time.perf_counter() - tr
-            write_png(f"{scene_name}_output_img/{cnt:06}.png", img)
+            if frame_colour is not None:
+                frame_colour_range = ps.frame_colour_range
+                write_png(f"{scene_name}_output_img/{cnt:06}.png", img,
+                          text={"field": frame_colour.field, "lo": repr(frame_colour_range[0]), "hi": repr(frame_colour_range[1]),
+                                "colormap": frame_colour.colormap_name()})
+            else:
+                write_png(f"{scene_name}_output_img/{cnt:06}.png", img)
             frames_written += 1
         if cnt % output_interval == 0:
             if output_ply:
@@ -200,6 +217,8 @@ def main(argv=None):
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
+        if frame_colour_range is not None:
+            report["frame_colour_range"] = list(frame_colour_range)     # of the last frame
     if particle_files:
         report["particle_files_written"] = particle_files
         report["export_ms_per_file"] = round(export_s / particle_files * 1e3, 4)
