@@ -176,7 +176,17 @@ enum SphOption {
                                   / density-advection sweep of an iteration also reduces compute_density_error()'s sum (DFSPH.py:224-230)
                                   over its own targets -- one f64 partial per brick, added up in brick-list order by the convergence
                                   test -- instead of a streaming kernel that re-reads every particle; 0 = that kernel (A/B).  The same
-                                  per-particle f32 terms either way; the f64 grouping differs (both deterministic). */
+                                  per-particle f32 terms either way; the f64 grouping differs (both deterministic). */,
+    SPH_OPT_SORT_FAST = 18     /* 1 = the sort at the head of a step of sph_step / sph_dfsph_step ranks the particles that STAY in their
+                                  cell from the previous order (previous cell array, a ballot of the movers) and compares only movers
+                                  and the members of cells with arrivals against those arrivals: no intra-cell offsets, no place
+                                  kernel, records read in order.  Taken only while the current order is a sort's output that nothing
+                                  has touched since (no upload, append, selection, truncate, window change), with SPH_OPT_SORT_BY_PID
+                                  and SPH_OPT_SLAB_DROP_OUTSIDE off; every other sort -- the first, stand-alone sph_sort /
+                                  sph_counting_sort, slab ranks -- is the general one.  0 = the general sort everywhere (A/B).  Same
+                                  order, same arrays, bit for bit.  sph_get_option reports the requested value. */,
+    SPH_OPT_SORT_FAST_COUNT = 19,   /* read-only: sorts of this context that ran on the fast path ... */
+    SPH_OPT_SORT_GENERAL_COUNT = 20 /* ... and on the general path (both wrap at 2^31) */
 };
 #define SPH_VAR_GROUPS 1   /* density: all nine runs filtered first (masks in registers), hits emitted centre run / edge runs / corner
                               runs, each group by descending hit count */

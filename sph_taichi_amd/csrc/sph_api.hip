@@ -86,7 +86,8 @@ int sph_check_device_flags(SphContext* c) {
         ((volatile int*)c->h_pinned)[16] = 0;
         c->sorted = c->have_prefix = c->have_keys = false;
         sph_invalidate_lists(c);
-        return sph_fail(c, SPH_E_STATE, "prefix sum: a scan tile never saw a predecessor's total (k_scan_fused's bounded wait ran out); "
+        sphd_records_moved(c->dv);
+        return sph_fail(c, SPH_E_STATE, "sort: a scan tile never saw a predecessor's total (k_scan_fused's bounded wait ran out), or a fast sort met a rank outside the arrays; "
                                         "the cell table of that sort and every result since are invalid: re-upload the state and sort again");
     }
     return 0;
@@ -304,6 +305,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     c->opt_brick_shape = 0;
     c->opt_rigid_batch = 1;
     c->opt_df_fuse_err = 1;
+    c->opt_sort_fast = SPH_SORT_FAST_DEFAULT;
     c->opt_df_runahead = 0;   // measured (r05): running ahead costs 2 % more than the bubbles it removes
     c->opt_exact_math = 0;
     c->opt_rigid_x0 = 0;
@@ -334,7 +336,11 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     rc = rc ? rc : alloc_dev(c, (void**)&c->acc_fx, cap * 3 * sizeof(long long));  // all zero except between a coupling sweep and its fold
     rc = rc ? rc : alloc_dev(c, (void**)&c->cell_buf[0], (size_t)c->scan_blocks * SCAN_TILE * 4);
     rc = rc ? rc : alloc_dev(c, (void**)&c->cell_buf[1], (size_t)c->scan_blocks * SCAN_TILE * 4);
-    if (!rc) { c->cell_cur = 0; c->cell_end = c->cell_buf[0]; c->next_cells_zero = false; }
+    rc = rc ? rc : alloc_dev(c, (void**)&c->cell_buf[2], (size_t)c->scan_blocks * SCAN_TILE * 4);
+    rc = rc ? rc : alloc_dev(c, (void**)&c->head_buf[0], (size_t)c->scan_blocks * SCAN_TILE * 4);
+    rc = rc ? rc : alloc_dev(c, (void**)&c->head_buf[1], (size_t)c->scan_blocks * SCAN_TILE * 4);
+    if (!rc) { c->cell_cur = 0; c->cell_prev = 2; c->cell_next = 1; c->cell_end = c->cell_buf[0]; c->next_cells_zero = false; }
+    if (!rc) { c->head_cur = 0; c->next_heads_zero = true; c->sort_fast_pending = false; c->n_sort_fast = c->n_sort_general = 0; }
     rc = rc ? rc : alloc_dev(c, (void**)&c->rank_off, cap * 4);
     rc = rc ? rc : alloc_dev(c, (void**)&c->idx_unstable, cap * 4);
     rc = rc ? rc : alloc_dev(c, (void**)&c->scan_status, (size_t)(c->scan_blocks + 1) * 8);
@@ -414,7 +420,7 @@ int32_t sph_destroy(SphContext* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->xm[0], c->xm[1], c->vf[0], c->vf[1], c->aux[0], c->aux[1], c->key[0], c->key[1], c->eos, c->stg, c->gat, c->acc,
-                    c->acc_tmp, c->cell_buf[0], c->cell_buf[1], c->rank_off, c->idx_unstable, c->scan_status, c->x0_cold, c->color_cold,
+                    c->acc_tmp, c->cell_buf[0], c->cell_buf[1], c->cell_buf[2], c->head_buf[0], c->head_buf[1], c->rank_off, c->idx_unstable, c->scan_status, c->x0_cold, c->color_cold,
                     c->rigid_rest_cm, c->dyn_list, c->dyn_count, c->acc_fx, c->rigid_part, c->rigid_R, c->df_err, c->df_part, c->df_bpart, c->stage, c->glist, c->gcnt, c->brick_list, c->brick_count, c->brick_list2, c->brick_count2, c->brick_rec};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     sph_render_release(c);
@@ -470,6 +476,7 @@ int32_t sph_set_option(SphContext* c, int32_t option, int32_t value) {
             c->opt_pure_instance = value; sph_invalidate_lists(c); return 0;
         case SPH_OPT_BRICK_RECORDS: c->opt_brick_rec = value ? 1 : 0; sph_invalidate_lists(c); return 0;
         case SPH_OPT_DF_FUSE_ERROR: c->opt_df_fuse_err = value ? 1 : 0; return 0;
+        case SPH_OPT_SORT_FAST: c->opt_sort_fast = value ? 1 : 0; return 0;
     }
     return sph_fail(c, SPH_E_INVALID, "unknown option");
 }
@@ -497,6 +504,9 @@ int32_t sph_get_option(const SphContext* c, int32_t option, int32_t* value) {
         case SPH_OPT_PURE_FLUID_INSTANCE: *value = c->opt_pure_instance; return 0;
         case SPH_OPT_BRICK_RECORDS: *value = c->opt_brick_rec; return 0;
         case SPH_OPT_DF_FUSE_ERROR: *value = c->opt_df_fuse_err; return 0;
+        case SPH_OPT_SORT_FAST: *value = c->opt_sort_fast; return 0;
+        case SPH_OPT_SORT_FAST_COUNT: *value = c->n_sort_fast; return 0;
+        case SPH_OPT_SORT_GENERAL_COUNT: *value = c->n_sort_general; return 0;
     }
     return SPH_E_INVALID;
 }
@@ -556,6 +566,7 @@ int32_t sph_upload(SphContext* c, int32_t field, const void* host, size_t bytes)
     SPH_HIP(c, hipMemcpyAsync(c->stage, host, bytes, hipMemcpyHostToDevice, c->stream));
     int rc = sphk_insert(c, field, c->stage);
     if (rc) return rc;
+    sphd_records_moved(c->dv);   // records overwritten from the host: the next sort is the general one
     SPH_HIP(c, hipStreamSynchronize(c->stream));  // host buffer is only borrowed for the call
     if (field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC || field == SPH_F_DENSITY) c->n_dyn_host = -1;  // (density: the scale of the rigid sums)
     if (field == SPH_F_MATERIAL || field == SPH_F_M || field == SPH_F_M_V) c->uniform_state = -1;
@@ -617,13 +628,17 @@ static int refresh_dyn(SphContext* c) {
     if (!(c)) return SPH_E_INVALID;               \
     SPH_HIP((c), hipSetDevice((c)->device));
 
-int32_t sph_update_grid_id(SphContext* c) {
-    ENTER(c);
-    int rc = sphk_hash_histogram(c);
+static int update_grid_id(SphContext* c, bool allow_fast) {
+    int rc = sphk_hash_histogram(c, allow_fast);
     if (rc) return rc;
     c->have_keys = true;
     c->have_prefix = false;
     return 0;
+}
+
+int32_t sph_update_grid_id(SphContext* c) {
+    ENTER(c);
+    return update_grid_id(c, false);   // a stand-alone hash pass is today's: its caller may sort with the accelerations, or not at all
 }
 
 int32_t sph_prefix_sum(SphContext* c) {
@@ -637,8 +652,11 @@ int32_t sph_prefix_sum(SphContext* c) {
 
 static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets = nullptr) {
     if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_counting_sort before sph_prefix_sum");
+    const bool recount = c->n_dyn_host < 0;
     int rc = refresh_dyn(c);
     if (rc) return rc;
+    // (the fast hash pass zeroes the dynamic-solid counter, as the place kernel does behind this point on the general path)
+    if (recount && c->sort_fast_pending) SPH_HIP(c, hipMemsetAsync(c->dyn_count, 0, sizeof(int), c->stream));
     rc = sphk_sort_scatter(c, sort_acc, deliver_offsets);
     if (rc) return rc;
     c->in_off = 0;         // the scatter writes the other set from record 0
@@ -847,8 +865,8 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
 
 // hash + scan + scatter without touching aux: for callers that run a density sweep right behind it (nothing can read the
 // stale density / pressure copies the scatter moves in between; the acceleration is dead there too)
-static int sort_no_fold(SphContext* c, const CellIdx16* deliver_offsets = nullptr) {
-    int rc = sph_update_grid_id(c);
+static int sort_no_fold(SphContext* c, const CellIdx16* deliver_offsets = nullptr, bool allow_fast = false) {
+    int rc = update_grid_id(c, allow_fast && !deliver_offsets);
     rc = rc ? rc : sph_prefix_sum(c);
     return rc ? rc : counting_sort(c, false, deliver_offsets);
 }
@@ -873,7 +891,9 @@ int32_t sph_slab_set_window(SphContext* c, int32_t origin_x, int32_t nx) {
     // every cell id changes meaning: nothing derived from the old window survives, and the spare cell array was
     // zeroed for the old padded size only
     c->next_cells_zero = false;
+    c->next_heads_zero = false;
     sph_invalidate_lists(c);
+    sphd_records_moved(c->dv);
     c->have_keys = c->have_prefix = c->sorted = false;
     c->n_dyn_host = -1;
     return 0;
@@ -917,7 +937,7 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         const double t_end = c->sim_time + (double)c->p.dt;
         hipEvent_t* ev = nullptr;   // SPH_OPT_TIMING k: every k-th step carries the five events
         rc = timed_step_begin(c, &ev);
-        rc = rc ? rc : sort_no_fold(c);   // ps.initialize_particle_system()   sph_base.py:264
+        rc = rc ? rc : sort_no_fold(c, nullptr, true);   // ps.initialize_particle_system()   sph_base.py:264
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
         rc = body(c, ev, dynamic_ids, n_dynamic, it + 1 == n_steps);
@@ -1049,6 +1069,7 @@ int32_t sph_truncate(SphContext* c, int32_t n) {
     if (!c || n < 0 || n > c->N) return sph_fail(c, SPH_E_INVALID, "sph_truncate: out of range");
     if (n != c->N && !c->opt_no_dynamic) c->n_dyn_host = -1;  // the sort's list skipped the dropped strays: recount
     if (n != c->N) sph_forget_pure_fluid(c);   // (a truncate + append that restores N may bring solids in)
+    sphd_records_moved(c->dv);
     c->N = n;
     return 0;
 }
@@ -1079,6 +1100,7 @@ int32_t sph_append_records(SphContext* c, const void* src, int32_t count) {
     if (c->opt_uniform != 1) c->uniform_state = -1;  // arrivals are unchecked unless the caller vouches for them
     sph_forget_pure_fluid(c);   // ... and vouching is for a uniform fluid MASS only: arrivals may be solids
     sph_invalidate_lists(c);
+    sphd_records_moved(c->dv);
     c->have_keys = c->have_prefix = c->sorted = false;
     c->n_dyn_host = -1;
     return 0;

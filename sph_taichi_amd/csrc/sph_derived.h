@@ -16,6 +16,11 @@
 //                         change; a sort or a new record selection (other indices) ends that.
 //       df_bpart_valid    set and consumed inside one solver iteration, with nothing in between.
 //       brick_count_zero  describes the counter, not the particles.
+//   * The fast sort (sph_sort.hip: stayers ranked from the previous order) reads the previous sort's keys and cell array as
+//     the description of the CURRENT order.  That holds from a sort until records are moved, inserted, dropped, re-selected
+//     or overwritten from the host, or the grid window changes (sphd_records_moved); positions drifting under the advect do
+//     not end it -- that drift is what the next sort measures.  A sort that hashed strays into the virtual cell G leaves an
+//     order the fast path has no rule for.
 #pragma once
 
 // identity of a brick partition: the cut rule and the target x-layer ranges it was cut for
@@ -46,13 +51,17 @@ struct SphDerived {
     bool df_bpart_valid;    // the refresh sweep of this solver iteration left its per-brick density-error partials
     bool aux_stale;         // density / pressure of the fluid live in eos2 (lean density finish), not yet in aux
     bool brick_count_zero;  // brick_count is zero (hash kernel) and no list has been built into it since
+    bool order_from_sort;   // the current record order is a sort's output under the current key and cell arrays, without strays in cell G
 };
 
 // ---- events ----------------------------------------------------------------------------------------------------------
 // positions, flags, the particle set or an option the sweeps' instances depend on changed; also the scan's error flag
 static inline void sphd_invalidate(SphDerived& s) { s.lists_valid = s.bricks_valid = s.brec_valid = false; s.stg_kind = s.k_kind = 0; }
 // ... and the records were re-based (sph_set_particle_count, sph_select_range): eos2 is indexed from the old first record
-static inline void sphd_set_changed(SphDerived& s) { sphd_invalidate(s); s.aux_stale = false; }
+static inline void sphd_set_changed(SphDerived& s) { sphd_invalidate(s); s.aux_stale = false; s.order_from_sort = false; }
+// records were overwritten from the host, appended, dropped, or the cell ids changed meaning: the previous sort's keys and
+// cell array no longer describe the current order
+static inline void sphd_records_moved(SphDerived& s) { s.order_from_sort = false; }
 // a sort has been enqueued; `built`: its place kernel cut the step's partition under `key` (into the zeroed counter)
 static inline void sphd_sorted(SphDerived& s, bool built, const SphPartKey& key) {
     sphd_set_changed(s);  // (eos2 is in the old order: whoever needed density / pressure called sph_ensure_aux before)
@@ -61,6 +70,10 @@ static inline void sphd_sorted(SphDerived& s, bool built, const SphPartKey& key)
     s.bricks_valid = built;
     if (built) s.bricks_key = key;
 }
+// a hash pass has been enqueued: the current cell array is a histogram in the making, no longer the last sort's
+static inline void sphd_hash_started(SphDerived& s) { s.order_from_sort = false; }
+// ... and that sort ran to its end: its output order, keys and cell array stand (strays: it hashed with drop_outside on)
+static inline void sphd_order_established(SphDerived& s, bool strays_possible) { s.order_from_sort = !strays_possible; }
 // a sweep cut a partition of its own into the main stream's list: the lists of the old one cannot be read through it
 static inline void sphd_partition_rebuilt(SphDerived& s, const SphPartKey& key) {
     s.lists_valid = s.brec_valid = false;
@@ -98,3 +111,8 @@ static inline bool sphd_stats_have_lists(const SphDerived& s) { return s.gcnt_wr
 static inline bool sphd_bpart_ready(const SphDerived& s) { return s.df_bpart_valid; }
 static inline bool sphd_aux_in_eos2(const SphDerived& s) { return s.aux_stale; }
 static inline bool sphd_count_is_zero(const SphDerived& s) { return s.brick_count_zero; }
+// may the next sort rank stayers from the previous order (SPH_OPT_SORT_FAST)?  Only under the reference's intra-cell order
+// (previous index) and without the virtual cell
+static inline bool sphd_sort_fast_usable(const SphDerived& s, bool opt_fast, bool sort_by_pid, bool drop_outside) {
+    return opt_fast && s.order_from_sort && !sort_by_pid && !drop_outside;
+}

@@ -28,6 +28,7 @@
 #define SPH_MAX_TIMED_STEPS 128
 #define SPH_GLIST_ROWS 96  // list entries allocated per particle (24 groups of four); lists up to LISTCAP = 95 entries (developed dam-break flows reach 58, profiles/archive/r03i)
 #define SPH_DF_ERR_BLOCKS 512
+#define SPH_SORT_FAST_DEFAULT 1   // SPH_OPT_SORT_FAST when the caller does not choose (profiles/sort_fast_ab.json)
 #define SPH_VAR_PURE_INTERNAL 64   // not a user bit (sph_set_option refuses masks above 63): the pure-fluid instances of the density sweep and of the one-gather force sweep
 #define SPH_VAR_DEFAULT (SPH_VAR_GROUPS | SPH_VAR_FORCE_BF | SPH_VAR_DEEP)  // SPH_OPT_KERNEL_VARIANT when the caller does not choose: the fastest rows of profiles/archive/r03f_variants_partition_x_emission.json (density) and r02g_variants_force.json (force)
 
@@ -124,11 +125,20 @@ struct SphContext {
     float4* acc_tmp;
     long long* acc_fx;   // [3 cap] fixed-point accumulators of the coupling reactions
     int* cell_end;     // [G+1] the CURRENT cell array (one of cell_buf[])
-    int* cell_buf[2];  // two cell arrays: while one serves the sweeps, the scatter zeroes the other for the next histogram
+    int* cell_buf[3];  // cell arrays: while one serves the sweeps, the scatter zeroes another for the next histogram.  The general sort
+                       // rotates two of them; the fast sort reads the PREVIOUS array inside its scatter too, so it zeroes the third
     int cell_cur;
-    bool next_cells_zero;  // cell_buf[cell_cur ^ 1] is all zero (no memset needed before the next histogram)
-    int* rank_off;     // [cap] arbitrary intra-cell offset from the histogram atomics
-    int* idx_unstable; // [cap]
+    int cell_prev;     // the array that was current before the last hash pass
+    int cell_next;     // the array the next hash pass counts into
+    bool next_cells_zero;  // cell_buf[cell_next] is all zero (no memset needed before the next histogram)
+    int* head_buf[2];  // [G] fast sort: per cell, 1 + old index of the last arrival hashed into it (0: none); the arrivals chain through idx_unstable
+    int head_cur;      // the array the last fast hash pass wrote
+    bool next_heads_zero;  // head_buf[head_cur ^ 1] is all zero
+    bool sort_fast_pending;  // the last hash pass was the fast one: scan and scatter must be too
+    int opt_sort_fast;       // SPH_OPT_SORT_FAST
+    int n_sort_fast, n_sort_general;  // sorts run to their end, by path (SPH_OPT_SORT_FAST_COUNT / _GENERAL_COUNT)
+    int* rank_off;     // [cap] arbitrary intra-cell offset from the histogram atomics (fast sort: the NEW key of every old index)
+    int* idx_unstable; // [cap] (fast sort: next arrival of the same cell, as 1 + old index, at a mover's old index)
     unsigned long long* scan_status;  // per scan tile: launch epoch << 32 | tile total (k_scan_fused)
     unsigned scan_epoch;
     int* scan_err;     // raised by a scan tile that never saw a predecessor's total (a bounded wait, never a hang)
@@ -244,7 +254,7 @@ int sph_check_device_flags(SphContext* c);
 #define SPH_LAUNCH_CHECK(ctx) SPH_HIP(ctx, hipGetLastError())
 
 // ---- launch entry points implemented in the .hip files --------------------
-int sphk_hash_histogram(SphContext* c);
+int sphk_hash_histogram(SphContext* c, bool allow_fast = false);  // allow_fast: the caller's sort may take the fast path when the derived state permits it
 int sphk_scan(SphContext* c);
 int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets);  // non-null: the place kernel also hands these scanned cells to the host
 int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, double* out);
