@@ -763,6 +763,86 @@ int32_t sph_field_range(SphContext* ctx, const SphFieldColour* colour, SphFieldR
  * where the pixel holds no field-coloured fluid; SPH_E_STATE if the last surface frame had none.  Synchronises. */
 int32_t sph_frame_download_field_index(SphContext* ctx, int32_t* index, size_t bytes);
 
+/* ======================================================================================
+ * Field sampling (the reference has none; its validation cases report pressure at a sensor, a velocity profile in a section, a
+ * regular volume for a viewer): SPH interpolation of velocity, density and pressure AT PLACES -- the nodes of a regular grid (a
+ * volume; a slice when one n[a] is 1) or up to SPH_SAMPLE_MAX_POINTS probe points -- by SCATTER: one streaming pass over the live
+ * records in their current order in which every selected particle adds its kernel-weighted share to the sample positions inside
+ * its support radius.  No neighbour search: the cell array, which describes the positions of the last sort, is never read.
+ * SELECTED: as in the export, a particle whose material equals `material` (unless -1) and whose object id is in
+ * object_ids[0..n_objects) (unless n_objects == 0).
+ * SAMPLE POSITIONS: grid node (k0, k1, k2), at index (k0 * n[1] + k1) * n[2] + k2, is p_a = origin_a + (float)k_a * spacing_a: one
+ * multiply, one add, not contracted.  A probe point is the f32 triple as given.
+ * PAIR TERM of sample position p and selected particle j: f32, in this order, nothing contracted into an fma:
+ *     dx = p.x - x_j.x (dy, dz alike);  r2 = (dx*dx + dy*dy) + dz*dz;  r = correctly rounded sqrtf(r2);  q = r * inv_h
+ *     the pair contributes  <=>  q <= 1.0f                    (a NaN does not contribute)
+ *     W = q <= 0.5f ? k_w * ((6.f*q3 - 6.f*q2) + 1.f)         with q2 = q*q, q3 = q2*q
+ *                   : (k_w * 2.f) * ((t*t)*t)                 with t = 1.f - q
+ *     w = fminf(fmaxf(m_V_j * W, 0.f), 4.f)
+ * the reference's cubic_kernel (sph_base.py:24-44) with the context's folded constant k_w.  inv_h is computed by the caller (the
+ * Python layer: f32(1) / f32(support_radius)) and passed by value, as inv_cell is for the column maps.  m_V is the particle's own
+ * volume: m_V0 for fluid, the boundary volume for solids.  The weights never read a density, so they are valid before the first
+ * step and never stale.
+ * ACCUMULATION per sample position, all sums i64 (llrint: round to nearest even):
+ *     count  += 1
+ *     weight += llrint((double)w * 2^30)
+ *     sum[f] += llrint(((double)w * (double)fmaxf(fminf(A_f, 2^24), -2^24)) * 2^30)      for every requested field f
+ * the fields being the bits of `fields` in the order vx vy vz density pressure.  The f64 product of two f32 values is exact and so is
+ * the scaling: each term rounds once.  BOUND: for every state the library produces w <= 1 (fluid: m_V0 * k_w = 0.8 * 8 / (8 pi) <
+ * 0.255; a boundary volume is at most 1 / k_w), so a term is below 2^54 and an i64 holds 2^9 contributors AT THE CLAMP, against about
+ * 34 at rest spacing; with the clamp of w at 4 (uploaded volumes) a term is below 2^56 and 2^7 such contributors fit.  `count` is
+ * downloaded so that a caller can see the occupancy.  A value is sum[f] / weight where weight != 0; weight / 2^30 is the Shepard
+ * sum, 0.8 inside a fluid at rest spacing (m_V0 = 0.8 d^3).
+ * FRESHNESS: x, v, density and pressure are the values sph_download would return at that moment.  After sph_step, x and v are
+ * end-of-step values; density and pressure are those of the step's density sweep, one dt behind.  When density or pressure is
+ * requested, what a fused step left in its own record is materialised first (as the diagnostics do and as any download of them
+ * does); otherwise NOTHING of the context is written.  A run with sample calls between its steps ends bit-identical to the run
+ * without.
+ * DETERMINISTIC: every accumulation is an integer sum, so the result is the same bits for any particle order, grouping and
+ * scheduling; there is no float or double atomic anywhere.  csrc/sph_sample.hip describes the footprints and the kernels.
+ * sph_sample_grid enqueues clear plus scatter on the context's stream; sph_sample_grid_download copies the planes of the LAST grid
+ * (weight [nodes], count [nodes], sums [F][nodes] with F the number of requested fields; any pointer may be NULL) and synchronises.
+ * sph_sample_points copies the m points (xyz: host pointer, [m][3], free again when the call returns), enqueues clear plus scatter;
+ * sph_sample_points_download returns the same planes over m.  Buffers are allocated by the first call, the grid's again when a
+ * later grid needs more, and freed with the context; a context that never samples allocates nothing.
+ * SPH_E_INVALID: n[a] < 1; more than SPH_SAMPLE_MAX_NODES nodes; m outside [1, SPH_SAMPLE_MAX_POINTS]; a non-finite origin or point;
+ * a spacing that is not finite and positive; a spacing below support_radius / 8 (that bounds a particle's footprint at 17^3 nodes; a
+ * slice still gives a spacing for its axis; the footprints are built with 1 / inv_h, so spacing * inv_h below 1 / 8 is refused
+ * alike); an inv_h that is not finite and positive; unknown field bits; material outside [-1, 255] or n_objects outside
+ * [0, SPH_SAMPLE_MAX_OBJECTS]; for a download a size that does not match the last call.  A refused call changes nothing: the last
+ * good result stays downloadable.  SPH_E_STATE: a download before any sample; single-domain contexts only: a slab rank, whose ghost
+ * records would be counted twice, answers SPH_E_STATE.  (The diagnostics also refuse a context whose last sph_slab_forces left the
+ * acceleration partly written; that case does not arise here: the acceleration is not read.)
+ * ==================================================================================== */
+#define SPH_SAMPLE_VX       1
+#define SPH_SAMPLE_VY       2
+#define SPH_SAMPLE_VZ       4
+#define SPH_SAMPLE_DENSITY  8
+#define SPH_SAMPLE_PRESSURE 16
+#define SPH_SAMPLE_MAX_NODES (1 << 24)
+#define SPH_SAMPLE_MAX_POINTS 1024
+#define SPH_SAMPLE_MAX_OBJECTS 32
+#define SPH_SAMPLE_SCALE_LOG2 30
+typedef struct SphSampleSelect {
+    int32_t material;               /* -1: any; else == the particle's SPH_F_MATERIAL */
+    int32_t n_objects;              /* 0: every object; else the particle's object id must be in object_ids[0..n) */
+    int32_t object_ids[SPH_SAMPLE_MAX_OBJECTS];
+} SphSampleSelect;
+typedef struct SphSampleGrid {
+    int32_t n[3];                   /* nodes per axis; n[0] * n[1] * n[2] <= SPH_SAMPLE_MAX_NODES */
+    float origin[3], spacing[3];
+    float inv_h;                    /* f32(1) / f32(support_radius), computed by the caller */
+    int32_t fields;                 /* mask of SPH_SAMPLE_*; the sums' planes follow in THIS order */
+    SphSampleSelect select;
+} SphSampleGrid;
+int32_t sph_sample_grid(SphContext* ctx, const SphSampleGrid* grid);   /* enqueues */
+int32_t sph_sample_grid_download(SphContext* ctx, int64_t* weight, int64_t* count, int64_t* sums /* [F][nodes] */,
+                                 int64_t nodes);                        /* any pointer may be NULL; synchronises */
+int32_t sph_sample_points(SphContext* ctx, const float* xyz /* host, [m][3] */, int32_t m, int32_t fields,
+                          const SphSampleSelect* select, float inv_h);  /* enqueues */
+int32_t sph_sample_points_download(SphContext* ctx, int64_t* weight, int64_t* count, int64_t* sums /* [F][m] */,
+                                   int32_t m);                          /* any pointer may be NULL; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

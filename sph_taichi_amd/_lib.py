@@ -142,6 +142,21 @@ class SphFieldRange(C.Structure):
     _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("count", C.c_int64), ("non_finite", C.c_int64)]
 
 
+class SphSampleSelect(C.Structure):
+    """Mirror of `struct SphSampleSelect` (include/sph_hip.h)."""
+    _fields_ = [("material", C.c_int32), ("n_objects", C.c_int32), ("object_ids", C.c_int32 * 32)]
+
+
+class SphSampleGrid(C.Structure):
+    """Mirror of `struct SphSampleGrid` (include/sph_hip.h)."""
+    _fields_ = [("n", C.c_int32 * 3), ("origin", _F3), ("spacing", _F3), ("inv_h", C.c_float), ("fields", C.c_int32),
+                ("select", SphSampleSelect)]
+
+
+# field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
+SAMPLE_VX, SAMPLE_VY, SAMPLE_VZ, SAMPLE_DENSITY, SAMPLE_PRESSURE = 1, 2, 4, 8, 16
+SAMPLE_MAX_NODES, SAMPLE_MAX_POINTS, SAMPLE_MAX_OBJECTS, SAMPLE_SCALE_LOG2 = 1 << 24, 1024, 32, 30
+
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
     F_IS_DYNAMIC, F_GRID_IDS, F_GRID_PARTICLES_NUM, F_PID, F_RIGID_REST_CM, F_DFSPH_FACTOR, F_DENSITY_ADV = range(18)
@@ -269,6 +284,10 @@ SYMBOLS = [
     ("sph_frame_set_colour", C.c_int32, [_ctx, C.POINTER(SphFieldColour), C.c_void_p]),
     ("sph_field_range", C.c_int32, [_ctx, C.POINTER(SphFieldColour), C.POINTER(SphFieldRange)]),
     ("sph_frame_download_field_index", C.c_int32, [_ctx, C.c_void_p, C.c_size_t]),
+    ("sph_sample_grid", C.c_int32, [_ctx, C.POINTER(SphSampleGrid)]),
+    ("sph_sample_grid_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    ("sph_sample_points", C.c_int32, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SphSampleSelect), C.c_float]),
+    ("sph_sample_points_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
 ]
 
 _LIB = None

@@ -434,6 +434,24 @@ class ParticleSystem:
         from . import export as _export
         return _export.export(self, objects=objects, material=material, fields=fields, box=box, every=every, phase=phase)
 
+    def sample_grid(self, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None):
+        """The SPH interpolation of `fields` (names from velocity, density, pressure) at the nodes origin + k * spacing of a
+        regular grid (sample.FieldGrid: raw i64 planes `weight`, `count`, `sums`; `fill`, `velocity`, `density`, `pressure`,
+        `wet()` follow from them; `write_vtk(path)`).  `spacing` (one number or one per axis) defaults to the particle
+        diameter, `origin` to 0, `shape` to the nodes that cover the domain; a slice is a shape with a 1 in it.  `material`:
+        "fluid" (default), "solid", an id or None (any; solids then contribute with their boundary volumes); `objects`: ids to
+        keep (None: all).  x and v are the current values; density and pressure are those of the last step's density sweep,
+        one dt behind.  One streaming pass on the device behind whatever was enqueued; only the planes are copied back
+        (synchronises).  Reads the records; changes nothing a later step reads."""
+        from . import sample as _sample
+        return _sample.sample_grid(self, spacing=spacing, origin=origin, shape=shape, fields=fields, material=material, objects=objects)
+
+    def sample_points(self, points, fields=("velocity",), material="fluid", objects=None):
+        """The same interpolation at up to 1024 probe points [[x, y, z], ...] (sample.FieldProbes: the same planes and views per
+        point, `rows()` for JSON)."""
+        from . import sample as _sample
+        return _sample.sample_points(self, points, fields=fields, material=material, objects=objects)
+
     def build_time_step_controller(self, solver):
         """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""
         from . import timestep as _timestep

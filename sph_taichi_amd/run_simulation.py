@@ -33,6 +33,11 @@ defaults of render.SurfaceStyle.  Absent or "spheres": the frames are what they 
 "field" is needed; `--frame_colour FIELD` is the short form) colours the selected particles of either frame style by a field
 (render.FieldColour); without "range" each frame takes the range of its own particles, reduced on the device.  Each PNG then
 carries field, lo, hi and colormap as tEXt chunks, and the final report holds `frame_colour_range`, the range of the last frame.
+A Configuration with "sampleGrid": {"spacing": s, "origin": [..], "shape": [..], "fields": ["velocity", "pressure"], "objects": [0]}
+(every key optional) writes `{scene}_output/grid_{cnt:06}.vtk` per exported interval: the fluid's fields interpolated on a regular
+grid on the device (sample.py), a legacy binary STRUCTURED_POINTS volume.  "probes": {"points": [[x, y, z], ...], "fields": [...]}
+with `--probes PATH` writes one JSON line per exported interval: frame, time and one row per point (count, fill, the fields).
+Without the keys nothing changes.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -72,6 +77,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gauges", default="", metavar="PATH",
                     help="write one JSON line per exported interval here: frame, time, wet extent, selected / outside, and the "
                          "scene's gauge points read off a column map")
+    ap.add_argument("--probes", default="", metavar="PATH",
+                    help="write one JSON line per exported interval here: frame, time and the scene's \"probes\" points sampled "
+                         "from the fluid (count, fill, the fields)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
                     help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
@@ -103,7 +111,12 @@ def main(argv=None):
         os.makedirs(f"{scene_name}_output_img", exist_ok=True)
     from . import export as _export
     export_spec = _export.export_config(config)        # "exportParticles": None when the key is absent
-    if output_ply or output_obj or export_spec is not None:
+    from . import sample as _sample
+    grid_spec = _sample.sample_grid_config(config)     # "sampleGrid": None when the key is absent
+    probes_spec = _sample.probes_config(config) if args.probes else None
+    if args.probes and probes_spec is None:
+        raise ValueError('--probes needs a "probes" object in the scene\'s Configuration')
+    if output_ply or output_obj or export_spec is not None or grid_spec is not None:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -132,6 +145,7 @@ def main(argv=None):
         ps.set_option(_lib.OPT_TIMING, 1)
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
+    probes_out = open(args.probes, "w") if probes_spec is not None else None
     gauges = gauges_out = None
     if args.gauges or args.heightmap_dir:
         from . import columns as _columns
@@ -141,7 +155,7 @@ def main(argv=None):
         if args.heightmap_dir:
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
-    cnt = cnt_ply = frames_written = particle_files = 0
+    cnt = cnt_ply = frames_written = particle_files = grid_files = 0
     render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
@@ -163,6 +177,12 @@ def main(argv=None):
             if args.heightmap_dir:
                 write_heightmap(os.path.join(args.heightmap_dir, f"{cnt:06}.png"),
                                 _columns.heightmap_image(cmap, float(ps.domain_size[cmap.axis])))
+        if grid_spec is not None and cnt % output_interval == 0:
+            ps.sample_grid(**grid_spec).write_vtk(f"{scene_name}_output/grid_{cnt:06}.vtk")
+            grid_files += 1
+        if probes_out is not None and cnt % output_interval == 0:
+            probes = ps.sample_points(**probes_spec)
+            probes_out.write(json.dumps({"frame": cnt, "time": probes.time, "probes": probes.rows()}) + "\n")
         if output_frames and cnt % output_interval == 0:
             ps.sync()                          # the frame's cost, not the steps still in flight before it
             tr = time.perf_counter()
@@ -214,6 +234,10 @@ def main(argv=None):
         diag_out.close()
     if gauges_out is not None:
         gauges_out.close()
+    if probes_out is not None:
+        probes_out.close()
+    if grid_files:
+        report["grid_files_written"] = grid_files
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)

@@ -1,0 +1,355 @@
+"""Field sampling: what `ParticleSystem.sample_grid()` and `ParticleSystem.sample_points()` return, and the legacy VTK volume
+a grid writes (include/sph_hip.h, section "Field sampling"; csrc/sph_sample.hip).
+
+The SPH interpolation of velocity, density and pressure at places: the nodes of a regular grid (a volume, or a slice when the
+shape has a 1 in it) or a handful of probe points.  One streaming pass on the device in which every selected particle adds its
+kernel-weighted share to the sample positions inside its support radius; only the planes cross to the host.  The raw planes are
+i64 fixed-point sums (scale 2^30): `weight` = sum of w, `sums[f]` = sum of w * A_f, `count` = number of contributing particles;
+a value is sums[f] / weight.  Nothing in this module touches the GPU when it is imported: the library is reached through the
+ParticleSystem handed to `sample_grid` / `sample_points`.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+SCALE_LOG2 = 30                      # the sums are fixed point: llrint(w * 2^30), llrint(w * A * 2^30) per contributing pair
+MAX_NODES, MAX_POINTS, MAX_OBJECTS = 1 << 24, 1024, 32
+# user-level field -> the planes it asks for, in the order of the SPH_SAMPLE_* bits
+FIELD_PLANES = {"velocity": ("vx", "vy", "vz"), "density": ("density",), "pressure": ("pressure",)}
+PLANE_BITS = {"vx": 1, "vy": 2, "vz": 4, "density": 8, "pressure": 16}
+MATERIALS = {"solid": 0, "fluid": 1}
+GRID_CONFIG_KEYS = ("spacing", "origin", "shape", "fields", "objects")
+PROBES_CONFIG_KEYS = ("points", "fields")
+
+
+def _integer(value, name) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, not {value!r}")
+    return int(value)
+
+
+def _triple(value, name):
+    try:
+        a = np.asarray(value, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{name} must be one number or one per axis") from e
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3:
+        raise ValueError(f"{name} must be one number or one per axis")
+    with np.errstate(over="ignore"):
+        f = a.astype(np.float32)
+    if not np.isfinite(f).all():
+        raise ValueError(f"{name} must be finite (as f32)")
+    return tuple(float(v) for v in f)
+
+
+def select_args(fields=("velocity",), material="fluid", objects=None) -> dict:
+    """The selection and field arguments of `sample_grid` / `sample_points`, checked without a context: {"fields": names in
+    plane order, "planes": plane names, "mask", "material": -1 or the id, "objects": list}.  ValueError otherwise."""
+    if isinstance(fields, str):
+        raise ValueError("fields must be a sequence of names, not one string")
+    fields = list(fields)
+    unknown = [f for f in fields if f not in FIELD_PLANES]
+    if unknown:
+        raise ValueError(f"unknown field(s) {unknown}: choose from {list(FIELD_PLANES)}")
+    if len(set(fields)) != len(fields):
+        raise ValueError("a field is named twice")
+    names = tuple(n for n in FIELD_PLANES if n in fields)
+    planes = tuple(p for n in names for p in FIELD_PLANES[n])
+    mask = 0
+    for p in planes:
+        mask |= PLANE_BITS[p]
+    if material is None:
+        mat = -1
+    elif isinstance(material, str):
+        if material not in MATERIALS:
+            raise ValueError(f"material must be one of {list(MATERIALS)}, a material id or None (any), not {material!r}")
+        mat = MATERIALS[material]
+    else:
+        mat = _integer(material, "material")
+        if not 0 <= mat <= 255:
+            raise ValueError("a material id is in [0, 255]")
+    if objects is None:
+        ids = []
+    else:
+        if isinstance(objects, (int, np.integer)) and not isinstance(objects, (bool, np.bool_)):
+            objects = [objects]
+        ids = [_integer(o, "an object id") for o in objects]
+        if not ids:
+            raise ValueError("objects is empty: pass None for every object")
+        if len(ids) > MAX_OBJECTS:
+            raise ValueError(f"at most {MAX_OBJECTS} objects can be selected at once")
+        if min(ids) < 0:
+            raise ValueError("an object id is not negative")
+    return {"fields": names, "planes": planes, "mask": mask, "material": mat, "objects": ids}
+
+
+def grid_args(spacing=None, origin=None, shape=None, *, particle_diameter, domain_size) -> dict:
+    """Defaults resolved: spacing = the particle diameter (one number: all three axes), origin = 0, shape = the nodes that
+    cover the domain from the origin, ceil((domain_size - origin) / spacing) + 1 per axis.  Returns {"spacing", "origin"
+    (f32 values as float triples), "shape"}.  ValueError for what no grid can have."""
+    spacing = _triple(particle_diameter if spacing is None else spacing, "spacing")
+    if not all(s > 0 for s in spacing):
+        raise ValueError("spacing must be positive")
+    origin = _triple(0.0 if origin is None else origin, "origin")
+    if shape is None:
+        shape = tuple(max(int(math.ceil((float(domain_size[a]) - origin[a]) / spacing[a])) + 1, 1) for a in range(3))
+    else:
+        try:
+            shape = tuple(shape)
+        except TypeError as e:
+            raise ValueError("shape must be three node counts") from e
+        if len(shape) != 3:
+            raise ValueError("shape must be three node counts")
+        shape = tuple(_integer(n, "a node count") for n in shape)
+    if min(shape) < 1:
+        raise ValueError("every node count must be at least 1 (a slice is a shape with a 1 in it)")
+    if shape[0] * shape[1] * shape[2] > MAX_NODES:
+        raise ValueError(f"{shape[0]} x {shape[1]} x {shape[2]} nodes: a grid holds at most {MAX_NODES}")
+    return {"spacing": spacing, "origin": origin, "shape": shape}
+
+
+def points_arg(points) -> np.ndarray:
+    """Probe points as a contiguous f32 [m, 3]; ValueError unless 1 <= m <= 1024 and every coordinate is finite as f32."""
+    try:
+        p = np.asarray(points, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError("points must be a list of [x, y, z] triples") from e
+    if p.ndim == 1 and p.size == 3:
+        p = p.reshape(1, 3)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points must be a list of [x, y, z] triples")
+    if not 1 <= p.shape[0] <= MAX_POINTS:
+        raise ValueError(f"between 1 and {MAX_POINTS} points can be sampled at once, not {p.shape[0]}")
+    with np.errstate(over="ignore"):
+        f = np.ascontiguousarray(p, dtype=np.float32)
+    if not np.isfinite(f).all():
+        raise ValueError("points must be finite (as f32)")
+    return f
+
+
+def node_positions(origin, spacing, shape) -> np.ndarray:
+    """The kernel's node positions, f32 [n0, n1, n2, 3]: origin_a + f32(k_a) * spacing_a, one multiply and one add in f32."""
+    axes = [np.float32(origin[a]) + np.arange(shape[a], dtype=np.float32) * np.float32(spacing[a]) for a in range(3)]
+    return np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).astype(np.float32)
+
+
+class _Sampled:
+    """The raw planes over any shape -- `weight`, `count` i64 [...], `sums` i64 [F, ...] with F = len(planes) -- and the f64
+    views that follow from them."""
+
+    def __init__(self, weight, count, sums, planes, time):
+        self.weight = np.asarray(weight, dtype=np.int64)
+        self.count = np.asarray(count, dtype=np.int64).reshape(self.weight.shape)
+        self.planes = tuple(planes)
+        self.sums = np.asarray(sums, dtype=np.int64).reshape((len(self.planes),) + self.weight.shape)
+        self.fields = tuple(n for n in FIELD_PLANES if all(p in self.planes for p in FIELD_PLANES[n]))
+        self.time = float(time)
+
+    @property
+    def fill(self):
+        """The Shepard sum, weight / 2^30: 0.8 inside a fluid at rest spacing (m_V0 = 0.8 d^3), falling to 0 across its surface."""
+        return self.weight.astype(np.float64) / float(1 << SCALE_LOG2)
+
+    def wet(self, threshold: float = 0.5):
+        return self.fill >= float(threshold)
+
+    def _value(self, plane):
+        if plane not in self.planes:
+            raise ValueError(f"{plane} was not sampled: the fields are {list(self.fields)}")
+        s = self.sums[self.planes.index(plane)].astype(np.float64)
+        has = self.weight != 0
+        return np.where(has, s / np.where(has, self.weight, 1).astype(np.float64), np.nan)
+
+    @property
+    def velocity(self):
+        """[..., 3] f64: sum / weight, NaN where weight == 0."""
+        return np.stack([self._value(p) for p in FIELD_PLANES["velocity"]], axis=-1)
+
+    @property
+    def density(self):
+        return self._value("density")
+
+    @property
+    def pressure(self):
+        return self._value("pressure")
+
+
+class FieldGrid(_Sampled):
+    """One sampled grid: the raw planes [n0, n1, n2] plus `time`, `origin`, `spacing`, `shape`; `fill`, `velocity`, `density`,
+    `pressure`, `wet()` as f64 views; `write_vtk(path)`.  Node (k0, k1, k2) is at origin + k * spacing."""
+
+    def __init__(self, weight, count, sums, planes, *, time, origin, spacing, shape):
+        self.shape = tuple(int(n) for n in shape)
+        if len(self.shape) != 3:
+            raise ValueError("shape must be three node counts")
+        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.shape), count, sums, planes, time)
+        self.origin = _triple(origin, "origin")
+        self.spacing = _triple(spacing, "spacing")
+
+    @property
+    def positions(self):
+        return node_positions(self.origin, self.spacing, self.shape)
+
+    def vtk_arrays(self):
+        """(name, components, f32 array in VTK point order: x fastest) of what `write_vtk` writes: fill, then the fields."""
+        order = lambda a: np.ascontiguousarray(np.transpose(a, (2, 1, 0) + tuple(range(3, a.ndim))))
+        out = [("fill", 1, order(self.fill).astype(np.float32))]
+        for name in self.fields:
+            a = getattr(self, name)
+            out.append((name, 3 if name == "velocity" else 1, order(a).astype(np.float32)))
+        return out
+
+    def write_vtk(self, path):
+        """A legacy binary STRUCTURED_POINTS file: ASCII header, big-endian f32; `fill` and every scalar field as SCALARS,
+        the velocity as VECTORS.  Values where nothing contributed are NaN."""
+        n =self.shape[0] * self.shape[1] * self.shape[2]
+        head = ["# vtk DataFile Version 3.0", f"sph_taichi_amd field grid, time {self.time!r}", "BINARY", "DATASET STRUCTURED_POINTS",
+                "DIMENSIONS {} {} {}".format(*self.shape), "ORIGIN {!r} {!r} {!r}".format(*self.origin),
+                "SPACING {!r} {!r} {!r}".format(*self.spacing), f"POINT_DATA {n}"]
+        with open(path, "wb") as fh:
+            fh.write(("\n".join(head) + "\n").encode("ascii"))
+            for name, comps, a in self.vtk_arrays():
+                if comps == 3:
+                    fh.write(f"VECTORS {name} float\n".encode("ascii"))
+                else:
+                    fh.write(f"SCALARS {name} float 1\nLOOKUP_TABLE default\n".encode("ascii"))
+                fh.write(a.astype(">f4").tobytes())
+                fh.write(b"\n")
+
+
+class FieldProbes(_Sampled):
+    """The same views per probe point: raw planes [m], `points` f32 [m, 3]; `rows()` for JSON."""
+
+    def __init__(self, points, weight, count, sums, planes, *, time):
+        self.points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.points.shape[0]), count, sums, planes, time)
+
+    def rows(self):
+        """One JSON-ready dict per point: point, count, fill and the sampled fields (None where nothing contributed)."""
+        num = lambda v: None if math.isnan(v) else float(v)
+        views = {name: getattr(self, name) for name in self.fields}
+        fill = self.fill
+        out = []
+        for k in range(self.points.shape[0]):
+            row = {"point": [float(v) for v in self.points[k]], "count": int(self.count[k]), "fill": float(fill[k])}
+            for name, a in views.items():
+                row[name] = [num(v) for v in a[k]] if name == "velocity" else num(a[k])
+            out.append(row)
+        return out
+
+
+def _fields_from_spec(spec, key, default):
+    fields = spec.get("fields", default)
+    if isinstance(fields, str) or not isinstance(fields, (list, tuple)):
+        raise ValueError(f'"{key}": fields must be a list of names')
+    return tuple(fields)
+
+
+def sample_grid_config(config):
+    """The scene's "sampleGrid" object: {"spacing": s, "origin": [..], "shape": [..], "fields": [..], "objects": [..]}, every key
+    optional ({} = velocity on the default grid).  Returns the keyword arguments of `sample_grid`, or None when the key is
+    absent.  A misspelt key or a bad value raises ValueError."""
+    spec = config.get_cfg("sampleGrid")
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError('"sampleGrid" must be an object')
+    unknown = set(spec) - set(GRID_CONFIG_KEYS)
+    if unknown:
+        raise ValueError(f'"sampleGrid": unknown key(s) {sorted(unknown)}')
+    kw = {"spacing": spec.get("spacing"), "origin": spec.get("origin"), "shape": spec.get("shape"),
+          "fields": _fields_from_spec(spec, "sampleGrid", ("velocity",)), "objects": spec.get("objects")}
+    try:
+        select_args(fields=kw["fields"], objects=kw["objects"])
+        grid_args(kw["spacing"], kw["origin"], kw["shape"], particle_diameter=1.0, domain_size=(1.0, 1.0, 1.0))
+    except ValueError as e:
+        raise ValueError(f'"sampleGrid": {e}') from e
+    return kw
+
+
+def probes_config(config):
+    """The scene's "probes" object: {"points": [[x, y, z], ...], "fields": [..]}.  Returns the keyword arguments of
+    `sample_points`, or None when the key is absent.  A misspelt key or a bad value raises ValueError."""
+    spec = config.get_cfg("probes")
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError('"probes" must be an object')
+    unknown = set(spec) - set(PROBES_CONFIG_KEYS)
+    if unknown:
+        raise ValueError(f'"probes": unknown key(s) {sorted(unknown)}')
+    if "points" not in spec:
+        raise ValueError('"probes": points is missing')
+    try:
+        pts = points_arg(spec["points"])
+        fields = _fields_from_spec(spec, "probes", ("velocity",))
+        select_args(fields=fields)
+    except ValueError as e:
+        raise ValueError(f'"probes": {e}') from e
+    return {"points": pts.astype(np.float64).tolist(), "fields": fields}
+
+
+def inv_h_f32(support_radius) -> float:
+    """f32(1) / f32(support_radius): the factor handed to the kernels."""
+    return float(np.float32(1) / np.float32(support_radius))
+
+
+def make_select(args: dict):
+    """SphSampleSelect of checked arguments (`select_args`)."""
+    from . import _lib
+    s = _lib.SphSampleSelect()
+    s.material, s.n_objects = args["material"], len(args["objects"])
+    for k, oid in enumerate(args["objects"]):
+        s.object_ids[k] = oid
+    return s
+
+
+def download_grid_raw(ps, grid, n_planes):
+    """sph_sample_grid + sph_sample_grid_download: (weight, count, sums) as flat i64 arrays (synchronises)."""
+    import ctypes as C
+    ps._call("sph_sample_grid", C.byref(grid))
+    nodes = int(grid.n[0]) * int(grid.n[1]) * int(grid.n[2])
+    weight, count = np.empty(nodes, dtype=np.int64), np.empty(nodes, dtype=np.int64)
+    sums = np.empty((n_planes, nodes), dtype=np.int64)
+    ps._call("sph_sample_grid_download", weight.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+             sums.ctypes.data_as(C.c_void_p) if n_planes else None, nodes)
+    return weight, count, sums
+
+
+def _refuse_slab(ps):
+    if ps.slab is not None:
+        raise NotImplementedError("fields are sampled on single-domain contexts only: a slab rank's ghost records would be "
+                                  "counted twice (the planes of the ranks' owned ranges would have to be all-reduced)")
+
+
+def sample_grid(ps, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None) -> FieldGrid:
+    import ctypes as C
+    from . import _lib
+    sel = select_args(fields=fields, material=material, objects=objects)
+    ga = grid_args(spacing, origin, shape, particle_diameter=ps.particle_diameter, domain_size=ps.domain_size)
+    _refuse_slab(ps)
+    g = _lib.SphSampleGrid()
+    g.n = (C.c_int32 * 3)(*ga["shape"])
+    g.origin, g.spacing = (C.c_float * 3)(*ga["origin"]), (C.c_float * 3)(*ga["spacing"])
+    g.inv_h, g.fields, g.select = inv_h_f32(ps.support_radius), sel["mask"], make_select(sel)
+    weight, count, sums = download_grid_raw(ps, g, len(sel["planes"]))
+    return FieldGrid(weight, count, sums, sel["planes"], time=ps.time, origin=ga["origin"], spacing=ga["spacing"], shape=ga["shape"])
+
+
+def sample_points(ps, points, fields=("velocity",), material="fluid", objects=None) -> FieldProbes:
+    import ctypes as C
+    sel = select_args(fields=fields, material=material, objects=objects)
+    pts = points_arg(points)
+    _refuse_slab(ps)
+    m, n_planes = pts.shape[0], len(sel["planes"])
+    s = make_select(sel)
+    ps._call("sph_sample_points", pts.ctypes.data_as(C.c_void_p), m, sel["mask"], C.byref(s), inv_h_f32(ps.support_radius))
+    weight, count = np.empty(m, dtype=np.int64), np.empty(m, dtype=np.int64)
+    sums = np.empty((n_planes, m), dtype=np.int64)
+    ps._call("sph_sample_points_download", weight.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+             sums.ctypes.data_as(C.c_void_p) if n_planes else None, m)
+    return FieldProbes(pts, weight, count, sums, sel["planes"], time=ps.time)
