@@ -843,6 +843,53 @@ int32_t sph_sample_points(SphContext* ctx, const float* xyz /* host, [m][3] */, 
 int32_t sph_sample_points_download(SphContext* ctx, int64_t* weight, int64_t* count, int64_t* sums /* [F][m] */,
                                    int32_t m);                          /* any pointer may be NULL; synchronises */
 
+/* ======================================================================================
+ * Surface mesh (the reference offers exportPly, particles to be meshed elsewhere): the fluid surface as an indexed triangle mesh,
+ * by SURFACE NETS on a sampled grid -- one vertex per mixed cell, one quad per sign-changing grid edge.  (Named sph_mesh_: "surface"
+ * is the screen-space frame style.)
+ * INPUT: the weight plane of the LAST successful sph_sample_grid of the context (any fields, also none; the selection of that call
+ * decides what the surface encloses), with the n, origin and spacing of that grid.  Node (k0, k1, k2) has linear index
+ * L = (k0 * n1 + k1) * n2 + k2.  Every n[a] >= 2 is needed.
+ * THRESHOLD: T = llrint((double)iso * 2^30), iso an f32 that is finite and in (0, 4].  weight / 2^30 is about 0.8 inside a fluid at
+ * rest spacing and falls to 0 across the free surface.
+ * CAPPED FIELD: phi(node) = 0 if `cap` is set and the node lies on the outer layer of the grid (some k_a == 0 or k_a == n_a - 1),
+ * otherwise phi(node) = weight[node].  A node is INSIDE iff phi >= T.  With cap the mesh is closed wherever the fluid meets the
+ * grid's border; without it the mesh is open there.
+ * CELLS: cell c = (c0, c1, c2), 0 <= c_a <= n_a - 2, linear index (c0 * (n1 - 1) + c1) * (n2 - 1) + c2, is ACTIVE iff its 8 corners
+ * are neither all inside nor all outside.
+ * VERTEX of an active cell.  Its 12 edges are visited in this order: for axis a = 0, 1, 2, with b < c the other two axes, the
+ * corner bits (i_b, i_c) run (0,0), (1,0), (0,1), (1,1).  An edge from corner lo to lo + e_a CROSSES iff exactly one end is inside;
+ * its crossing parameter is t = (double)(T - phi_lo) / (double)(phi_hi - phi_lo), both differences formed in i64 first (exact:
+ * weights stay below 2^41 at the bound stated for the sampling: 2^9 contributors of at most 4 * 2^30); its crossing point in
+ * cell-local units has component a equal to t and components b, c equal to the corner bits.  The crossing points are summed per
+ * component in f64, in that order, starting from 0.0, and divided by the number m of crossing edges; u_a = (float)mean_a;
+ *     pos_a = origin_a + ((float)c_a + u_a) * spacing_a            in f32, not contracted.
+ * NORMAL of that vertex: g_a = the i64 sum over the cell's 4 edges along a of phi_hi - phi_lo; gd_a = (double)g_a;
+ * s = (gd0*gd0 + gd1*gd1) + gd2*gd2; n_a = (float)(-gd_a / sqrt(s)), and (0, 0, 0) when s == 0.  It points out of the fluid.
+ * VERTEX NUMBERING: active cells by ascending cell linear index.
+ * FACES: node k owns the three edges k -> k + e_a; the axis triples (a, b, c) are (0,1,2), (1,2,0), (2,0,1).  An owned edge emits a
+ * quad iff it crosses and k_a <= n_a - 2, 1 <= k_b <= n_b - 2, 1 <= k_c <= n_c - 2, that is, all four cells round it exist (with
+ * cap this holds for every crossing edge).  The quad's vertices are those of the cells with low corners C0 = k - e_b - e_c,
+ * C1 = k - e_c, C2 = k, C3 = k - e_b, all active by construction.  If lo is inside and hi outside the triangles are (C0, C1, C2),
+ * (C0, C2, C3), otherwise (C0, C3, C2), (C0, C2, C1).  Quads are ordered by ascending key 3 * L + a; quad q gives triangles 2q, 2q+1.
+ * So the whole result -- counts, positions, normals, index buffer -- is one function of the weight plane and (iso, cap), independent
+ * of scheduling.  csrc/sph_mesh.hip describes the kernels.
+ * sph_mesh_extract classifies, scans, and emits vertices and faces on the context's stream; it synchronises once (the counts size
+ * the buffers) and the counts are known when it returns.  sph_mesh_counts returns them; sph_mesh_download copies positions [V][3],
+ * normals [V][3] and triangles [T][3] (any pointer may be NULL; sizes 0 are fine) and synchronises.  The mesh lives in buffers of its
+ * own: a later sph_sample_grid changes nothing of a mesh already extracted.  Buffers grow only, are allocated on first use and freed
+ * with the context; a context that never meshes allocates nothing.  Nothing of the particle state and nothing of the sampler's
+ * planes is written.
+ * SPH_E_INVALID: a NULL spec; iso not finite or outside (0, 4]; a sampled grid with an n[a] < 2; download sizes that do not match
+ * the last extract.  SPH_E_STATE: no sampled grid yet; a slab rank; counts or download before any extract.  A refused call leaves
+ * the last good mesh downloadable.
+ * ==================================================================================== */
+typedef struct SphMeshSpec { float iso; int32_t cap; } SphMeshSpec;
+int32_t sph_mesh_extract(SphContext* ctx, const SphMeshSpec* spec);     /* on the last sampled grid; counts are known on return */
+int32_t sph_mesh_counts(SphContext* ctx, int64_t* vertices, int64_t* triangles);
+int32_t sph_mesh_download(SphContext* ctx, float* pos /*[V][3]*/, float* nrm /*[V][3]*/, int32_t* tri /*[T][3]*/,
+                          int64_t vertices, int64_t triangles);         /* any pointer may be NULL; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

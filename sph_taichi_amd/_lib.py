@@ -153,6 +153,11 @@ class SphSampleGrid(C.Structure):
                 ("select", SphSampleSelect)]
 
 
+class SphMeshSpec(C.Structure):
+    """Mirror of `struct SphMeshSpec` (include/sph_hip.h)."""
+    _fields_ = [("iso", C.c_float), ("cap", C.c_int32)]
+
+
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
 SAMPLE_VX, SAMPLE_VY, SAMPLE_VZ, SAMPLE_DENSITY, SAMPLE_PRESSURE = 1, 2, 4, 8, 16
 SAMPLE_MAX_NODES, SAMPLE_MAX_POINTS, SAMPLE_MAX_OBJECTS, SAMPLE_SCALE_LOG2 = 1 << 24, 1024, 32, 30
@@ -288,6 +293,9 @@ SYMBOLS = [
     ("sph_sample_grid_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     ("sph_sample_points", C.c_int32, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SphSampleSelect), C.c_float]),
     ("sph_sample_points_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("sph_mesh_extract", C.c_int32, [_ctx, C.POINTER(SphMeshSpec)]),
+    ("sph_mesh_counts", C.c_int32, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("sph_mesh_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
 ]
 
 _LIB = None

@@ -429,6 +429,7 @@ int32_t sph_destroy(SphContext* c) {
     sph_export_release(c);
     sph_surface_release(c);
     sph_sample_release(c);
+    sph_mesh_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);

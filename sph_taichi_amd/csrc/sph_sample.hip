@@ -32,6 +32,7 @@
 // tests every point of the chunk; the block's non-empty partials are added to the planes.
 #include <cmath>
 #include "sph_observe.h"
+#include "sph_sample_grid.h"
 
 #pragma clang fp contract(off)
 
@@ -47,6 +48,8 @@ struct SphSample {
     long long* grid;          // [2 + F][nodes]: count, weight, then the requested fields in mask order
     size_t grid_words;        // allocated
     long long grid_nodes;     // of the last sph_sample_grid
+    int grid_n[3];            // its geometry: what the mesh extraction (sph_mesh.hip) reads the weight plane with
+    float grid_origin[3], grid_spacing[3];
     int grid_fields;          // number of field planes of the last sph_sample_grid
     bool grid_have;
     void* pts_buf;            // one allocation: xyz [SPH_SAMPLE_MAX_POINTS][3] f32, then the planes [SG_MAX_CHANNELS][SPH_SAMPLE_MAX_POINTS]
@@ -255,6 +258,15 @@ __global__ __launch_bounds__(STPB) void k_sample_points(const float4* __restrict
 
 void sph_sample_release(SphContext* c) { sph_observe_release(c->sample, &SphSample::grid, &SphSample::pts_buf); }
 
+bool sph_sample_last_grid(const SphContext* c, SphSampledGrid* out) {
+    const SphSample* s = c->sample;
+    if (!s || !s->grid_have) return false;
+    out->weight = s->grid + s->grid_nodes;   // plane 1: count, WEIGHT, then the fields
+    out->nodes = s->grid_nodes;
+    for (int a = 0; a < 3; ++a) { out->n[a] = s->grid_n[a]; out->origin[a] = s->grid_origin[a]; out->spacing[a] = s->grid_spacing[a]; }
+    return true;
+}
+
 static int sample_state(SphContext* c, const char* who) {
     if (!sph_observe_state(c->sample)) { snprintf(c->err, sizeof(c->err), "%s: out of host memory", who); return SPH_E_NOMEM; }
     return 0;
@@ -337,6 +349,7 @@ int32_t sph_sample_grid(SphContext* c, const SphSampleGrid* p) {
         SPH_LAUNCH_CHECK(c);
     }
     s->grid_nodes = nodes;
+    for (int a = 0; a < 3; ++a) { s->grid_n[a] = g.n[a]; s->grid_origin[a] = g.origin[a]; s->grid_spacing[a] = g.spacing[a]; }
     s->grid_fields = q.channels - 2;
     s->grid_have = true;
     return 0;

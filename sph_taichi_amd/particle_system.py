@@ -452,6 +452,18 @@ class ParticleSystem:
         from . import sample as _sample
         return _sample.sample_points(self, points, fields=fields, material=material, objects=objects)
 
+    def surface_mesh(self, spacing=None, origin=None, shape=None, iso=0.4, cap=True, material="fluid", objects=None):
+        """The surface of the selected particles as an indexed triangle mesh (mesh.SurfaceMesh: `vertices`, `normals`,
+        `triangles`; `volume()`, `area()`, `is_closed()`, `write_ply(path)`): surface nets on the grid `sample_grid` would make
+        from the same `spacing`, `origin`, `shape` (every node count at least 2), `material` and `objects`.  The surface is
+        where the grid's fill (weight / 2^30) equals `iso`; the fill is about 0.8 inside a fluid at rest spacing, so the default
+        0.4 is half the interior fill.  `cap`: treat the grid's outer layer of nodes as empty, which closes the mesh where the
+        fluid meets the grid's border (without it the mesh is open there).  With material=None the solids join the surface.
+        The grid is sampled and the mesh built on the device behind whatever was enqueued; only the mesh is copied back
+        (synchronises).  Reads the records; changes nothing a later step reads."""
+        from . import mesh as _mesh
+        return _mesh.surface_mesh(self, spacing=spacing, origin=origin, shape=shape, iso=iso, cap=cap, material=material, objects=objects)
+
     def build_time_step_controller(self, solver):
         """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""
         from . import timestep as _timestep

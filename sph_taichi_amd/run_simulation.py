@@ -38,6 +38,9 @@ A Configuration with "sampleGrid": {"spacing": s, "origin": [..], "shape": [..],
 grid on the device (sample.py), a legacy binary STRUCTURED_POINTS volume.  "probes": {"points": [[x, y, z], ...], "fields": [...]}
 with `--probes PATH` writes one JSON line per exported interval: frame, time and one row per point (count, fill, the fields).
 Without the keys nothing changes.
+A Configuration with "exportMesh": {"spacing": s, "origin": [..], "shape": [..], "iso": 0.4, "cap": true, "objects": [0]} (every key
+optional) writes `{scene}_output/surface_{cnt:06}.ply` per exported interval: the fluid surface as an indexed triangle mesh with
+normals, extracted on the device from such a grid (mesh.py), a binary PLY.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -116,7 +119,9 @@ def main(argv=None):
     probes_spec = _sample.probes_config(config) if args.probes else None
     if args.probes and probes_spec is None:
         raise ValueError('--probes needs a "probes" object in the scene\'s Configuration')
-    if output_ply or output_obj or export_spec is not None or grid_spec is not None:
+    from . import mesh as _mesh
+    mesh_spec = _mesh.mesh_config(config)              # "exportMesh": None when the key is absent
+    if output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -155,7 +160,7 @@ def main(argv=None):
         if args.heightmap_dir:
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
-    cnt = cnt_ply = frames_written = particle_files = grid_files = 0
+    cnt = cnt_ply = frames_written = particle_files = grid_files = mesh_files = 0
     render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
@@ -180,6 +185,9 @@ def main(argv=None):
         if grid_spec is not None and cnt % output_interval == 0:
             ps.sample_grid(**grid_spec).write_vtk(f"{scene_name}_output/grid_{cnt:06}.vtk")
             grid_files += 1
+        if mesh_spec is not None and cnt % output_interval == 0:
+            ps.surface_mesh(**mesh_spec).write_ply(f"{scene_name}_output/surface_{cnt:06}.ply", comments=(f"frame {cnt}",))
+            mesh_files += 1
         if probes_out is not None and cnt % output_interval == 0:
             probes = ps.sample_points(**probes_spec)
             probes_out.write(json.dumps({"frame": cnt, "time": probes.time, "probes": probes.rows()}) + "\n")
@@ -238,6 +246,8 @@ def main(argv=None):
         probes_out.close()
     if grid_files:
         report["grid_files_written"] = grid_files
+    if mesh_files:
+        report["mesh_files_written"] = mesh_files
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
