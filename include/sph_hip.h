@@ -843,6 +843,46 @@ int32_t sph_sample_points(SphContext* ctx, const float* xyz /* host, [m][3] */, 
 int32_t sph_sample_points_download(SphContext* ctx, int64_t* weight, int64_t* count, int64_t* sums /* [F][m] */,
                                    int32_t m);                          /* any pointer may be NULL; synchronises */
 
+/* --------------------------------------------------------------------------------------
+ * Field sampling: gradients.  The Shepard interpolant A(p) = sum[f] / weight has an analytic gradient that is a ratio of sums of the
+ * same kind:   grad A(p) = ( sum_j grad w_j A_j  -  A(p) sum_j grad w_j ) / sum_j w_j.
+ * The gradient-carrying calls below add those sums to the planes of a sample; sum_j grad w_j alone is the gradient of the fill, so
+ * -grad fill / |grad fill| is the free-surface normal.  Vorticity, divergence, strain rate and the Q-criterion follow on the host
+ * from the velocity gradient (sample.py).
+ * GRADIENT TERM of a contributing pair (q <= 1.0f), from the dx, dy, dz, r, q of the pair term above: f32, in this order, nothing
+ * contracted into an fma:
+ *     D = q <= 0.5f ? (k_w * 6.f) * (q * (3.f*q - 2.f))
+ *                   : (k_w * 6.f) * (-(t*t))                  with t = 1.f - q
+ *     u = fmaxf(fminf(m_V_j * D, 0.f), -8.f)
+ *     e_b = r > 0.f ? d_b / r : 0.f                           b = x, y, z; the IEEE-correct f32 division
+ *     g_b = u * e_b
+ * D is dW/dq, the reference's cubic_kernel_derivative (sph_base.py) without its 1 / h factor and without the unit vector; D <= 0 on
+ * [0, 1].  The sums are therefore DIMENSIONLESS (h grad w): the host multiplies by inv_h.
+ * ACCUMULATION per sample position, i64, llrint as above:
+ *     G_b    += llrint((double)g_b * 2^30)
+ *     S_f,b  += llrint(((double)g_b * (double)fmaxf(fminf(A_f, 2^24), -2^24)) * 2^30)    for every field f of `gradients`
+ * A particle exactly on the sample position (r == 0) contributes to count, weight and the field sums as before and ZERO to every
+ * gradient sum.  BOUND: |D| <= 2 k_w (its extremum, at q = 1/3), so for every state the library produces |u| <= 2 m_V k_w: below
+ * 0.51 for fluid and at most 2 for a boundary volume; |e_b| <= 1.  A term is then at most 2^55 in magnitude (|u| = 2 together with
+ * a field at its clamp) and an i64 holds 2^8 - 1 such contributors, against about 34 at rest spacing; at the clamp of u at 8
+ * (uploaded volumes) a term is at most 2^57 and 2^6 - 1 such contributors fit.
+ * PLANES of one result, in this order: count, weight, the fields of `fields`, Gx Gy Gz, then S_f,x S_f,y S_f,z for every bit f of
+ * `gradients` in mask order: at most 2 + 5 + 3 + 15 = 25.  weight stays the second plane: the mesh extraction reads what it read.
+ * `gradients` is a mask of SPH_SAMPLE_* bits, each of which must also be in `fields` (its term needs that field's sum); 0 asks for
+ * the fill gradient alone.  The base planes of a gradient-carrying call come through sph_sample_grid_download /
+ * sph_sample_points_download and equal those of the plain call bit for bit; the gradient planes come through the two downloads
+ * below as [3 + 3 Fg][nodes] or [3 + 3 Fg][m], Fg the number of bits of `gradients`.  The plain calls run the kernels they ran
+ * before.  Everything said above about selection, freshness, determinism, buffers and what is written holds unchanged.
+ * SPH_E_INVALID: every refusal of the plain calls; unknown bits in `gradients`; a bit of `gradients` that is not in `fields`; a
+ * gradients download whose size does not match the last sample of that kind.  SPH_E_STATE: a gradients download before any
+ * sample of that kind, or when the last one carried no gradients; a slab rank.  A refused call changes nothing.
+ * ------------------------------------------------------------------------------------ */
+int32_t sph_sample_grid_gradients(SphContext* ctx, const SphSampleGrid* grid, int32_t gradients);   /* enqueues */
+int32_t sph_sample_grid_gradients_download(SphContext* ctx, int64_t* grads /* [3 + 3 Fg][nodes] */, int64_t nodes);   /* synchronises */
+int32_t sph_sample_points_gradients(SphContext* ctx, const float* xyz /* host, [m][3] */, int32_t m, int32_t fields, int32_t gradients,
+                                    const SphSampleSelect* select, float inv_h);                   /* enqueues */
+int32_t sph_sample_points_gradients_download(SphContext* ctx, int64_t* grads /* [3 + 3 Fg][m] */, int32_t m);        /* synchronises */
+
 /* ======================================================================================
  * Surface mesh (the reference offers exportPly, particles to be meshed elsewhere): the fluid surface as an indexed triangle mesh,
  * by SURFACE NETS on a sampled grid -- one vertex per mixed cell, one quad per sign-changing grid edge.  (Named sph_mesh_: "surface"

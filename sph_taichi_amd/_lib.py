@@ -161,6 +161,7 @@ class SphMeshSpec(C.Structure):
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
 SAMPLE_VX, SAMPLE_VY, SAMPLE_VZ, SAMPLE_DENSITY, SAMPLE_PRESSURE = 1, 2, 4, 8, 16
 SAMPLE_MAX_NODES, SAMPLE_MAX_POINTS, SAMPLE_MAX_OBJECTS, SAMPLE_SCALE_LOG2 = 1 << 24, 1024, 32, 30
+SAMPLE_MAX_CHANNELS = 2 + 5 + 3 + 15     # count, weight, five field planes, Gx Gy Gz, three planes per gradient bit
 
 # enum SphField
 F_OBJECT_ID, F_X, F_X_0, F_V, F_ACCELERATION, F_M_V, F_M, F_DENSITY, F_PRESSURE, F_MATERIAL, F_COLOR, \
@@ -293,6 +294,10 @@ SYMBOLS = [
     ("sph_sample_grid_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     ("sph_sample_points", C.c_int32, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SphSampleSelect), C.c_float]),
     ("sph_sample_points_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("sph_sample_grid_gradients", C.c_int32, [_ctx, C.POINTER(SphSampleGrid), C.c_int32]),
+    ("sph_sample_grid_gradients_download", C.c_int32, [_ctx, C.c_void_p, C.c_int64]),
+    ("sph_sample_points_gradients", C.c_int32, [_ctx, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SphSampleSelect), C.c_float]),
+    ("sph_sample_points_gradients_download", C.c_int32, [_ctx, C.c_void_p, C.c_int32]),
     ("sph_mesh_extract", C.c_int32, [_ctx, C.POINTER(SphMeshSpec)]),
     ("sph_mesh_counts", C.c_int32, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("sph_mesh_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),

@@ -30,6 +30,14 @@
 // Nothing depends on the order of the records: unsorted ones only spread the adds.
 // Points kernel (k_sample_points): the points of a chunk and one i64 partial per (channel, point) live in LDS; every selected particle
 // tests every point of the chunk; the block's non-empty partials are added to the planes.
+//
+// GRADIENTS (include/sph_hip.h, "Field sampling: gradients"): the gradient of the Shepard interpolant is a ratio of sums of the same
+// kind, so both kernels have a second instance (template parameter GRAD) that adds, per contributing pair, g_b = u * e_b to the planes
+// Gx Gy Gz and g_b * A_f to three planes per field whose gradient is asked for; sample_gradient() below is THE gradient term, fed with
+// the dx, dy, dz, r, q of sample_pair().  The planes of one result are count, weight, the fields, Gx Gy Gz, then x y z per gradient
+// bit in mask order: up to 2 + 5 + 3 + 15 = 25 channels.  The plain instances are the kernels as they were: a call without gradients
+// runs the same code.  The points kernel sizes its chunk from the channel count so that the block stays within the 34,816 B of LDS
+// the plain instance uses at most: 164 points at 25 channels.
 #include <cmath>
 #include "sph_observe.h"
 #include "sph_sample_grid.h"
@@ -39,7 +47,9 @@
 #define STPB 256
 #define SG_MAX_BLOCKS 1024
 #define SG_MAX_CHANNELS (2 + 5)   // count, weight, vx vy vz density pressure
+#define SG_MAX_GRAD_CHANNELS (3 + 3 * 5)   // Gx Gy Gz, then x y z per gradient bit
 #define SP_CHUNK 512              // points per LDS chunk: 512 * (12 + 7 * 8) B = 34,816 B
+#define SP_LDS_BYTES (SP_CHUNK * (12 + SG_MAX_CHANNELS * 8))   // the budget the gradient instance sizes its chunk from
 #define SP_MAX_BLOCKS 1024
 #define S_FIELD_LIMIT 16777216.f  // 2^24
 #define S_ALL_FIELDS (SPH_SAMPLE_VX | SPH_SAMPLE_VY | SPH_SAMPLE_VZ | SPH_SAMPLE_DENSITY | SPH_SAMPLE_PRESSURE)
@@ -51,10 +61,11 @@ struct SphSample {
     int grid_n[3];            // its geometry: what the mesh extraction (sph_mesh.hip) reads the weight plane with
     float grid_origin[3], grid_spacing[3];
     int grid_fields;          // number of field planes of the last sph_sample_grid
+    int grid_grads;           // number of gradient planes behind them: 0 (a plain sample) or 3 + 3 Fg
     bool grid_have;
-    void* pts_buf;            // one allocation: xyz [SPH_SAMPLE_MAX_POINTS][3] f32, then the planes [SG_MAX_CHANNELS][SPH_SAMPLE_MAX_POINTS]
+    void* pts_buf;            // one allocation: xyz [SPH_SAMPLE_MAX_POINTS][3] f32, then the planes [SG_MAX_CHANNELS + SG_MAX_GRAD_CHANNELS][SPH_SAMPLE_MAX_POINTS]
     long long* pts;
-    int pts_m, pts_fields;
+    int pts_m, pts_fields, pts_grads;
     bool pts_have;
     bool pts_copying;         // pts_host may still be read by the copy of the last sph_sample_points
     float pts_host[3 * SPH_SAMPLE_MAX_POINTS];
@@ -90,13 +101,16 @@ __device__ __forceinline__ bool sample_selected(int fl, const SampleSelect& s) {
     return true;
 }
 
+struct SamplePairGeom { float d[3], r, q; };   // what the gradient term reuses of the pair term
+
 // THE pair term: does particle X = (x, y, z, m_V) contribute to position p, and with which weight
-__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w) {
+__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w, SamplePairGeom& geom) {
     const float dx = px - X.x, dy = py - X.y, dz = pz - X.z;
     const float r2 = (dx * dx + dy * dy) + dz * dz;
     const float r = sqrtf(r2);   // the correctly rounded one (hipcc's default for sqrtf; __fsqrt_rn is the 1-ulp v_sqrt_f32 here)
     const float q = r * inv_h;
     if (!(q <= 1.0f)) return false;
+    geom.d[0] = dx; geom.d[1] = dy; geom.d[2] = dz; geom.r = r; geom.q = q;
     float W;
     if (q <= 0.5f) {
         const float q2 = q * q, q3 = q2 * q;
@@ -107,6 +121,29 @@ __device__ __forceinline__ bool sample_pair(float px, float py, float pz, const 
     }
     w = fminf(fmaxf(X.w * W, 0.f), 4.f);
     return true;
+}
+
+__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w) {
+    SamplePairGeom unused;
+    return sample_pair(px, py, pz, X, inv_h, k_w, w, unused);
+}
+
+// THE gradient term of a contributing pair: g_b = u * e_b, dimensionless (h grad w); zero on every axis when r == 0
+__device__ __forceinline__ void sample_gradient(const SamplePairGeom& p, float m_V, float k_w, float g[3]) {
+    const float q = p.q;
+    float D;
+    if (q <= 0.5f) {
+        D = (k_w * 6.f) * (q * (3.f * q - 2.f));
+    } else {
+        const float t = 1.f - q;
+        D = (k_w * 6.f) * (-(t * t));
+    }
+    const float u = fmaxf(fminf(m_V * D, 0.f), -8.f);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const float e = p.r > 0.f ? p.d[b] / p.r : 0.f;   // the IEEE-correct division (hipcc's default, as for sqrtf)
+        g[b] = u * e;
+    }
 }
 
 __device__ __forceinline__ float sample_clamp_field(float a) { return fmaxf(fminf(a, S_FIELD_LIMIT), -S_FIELD_LIMIT); }
@@ -144,8 +181,10 @@ __global__ __launch_bounds__(STPB) void k_sample_clear(u64* __restrict__ p, size
 
 // grid = ceil(tiles / tiles_per_block) blocks of four waves; block b takes the tiles (256 records each) [b, b + 1) * tiles_per_block.
 // All 64 lanes of a wave make every trip of the record loop (the ballot needs them).
-__global__ __launch_bounds__(STPB) void k_sample_grid(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
-                                                      int N, int tiles_per_block, SampleCommon q, SampleGridDev g) {
+// GRAD: the gradient-carrying instance; `gradients` is its mask of field bits (a subset of q.fields) and is not read otherwise.
+template <bool GRAD>
+__device__ __forceinline__ void sample_grid_body(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
+                                                 int N, int tiles_per_block, const SampleCommon& q, const SampleGridDev& g, int gradients) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool need_aux = (q.fields & (SPH_SAMPLE_DENSITY | SPH_SAMPLE_PRESSURE)) != 0;
     const long long first = (long long)blockIdx.x * tiles_per_block * STPB;
@@ -192,7 +231,8 @@ __global__ __launch_bounds__(STPB) void k_sample_grid(const float4* __restrict__
                 const float py = g.origin[1] + (float)k1 * g.spacing[1];
                 const float pz = g.origin[2] + (float)k2 * g.spacing[2];
                 float w;
-                if (!sample_pair(px, py, pz, Xj, q.inv_h, q.k_w, w)) continue;
+                SamplePairGeom geom;
+                if (!sample_pair(px, py, pz, Xj, q.inv_h, q.k_w, w, geom)) continue;
                 u64* dst = (u64*)g.planes + (((size_t)k0 * g.n[1] + k1) * g.n[2] + k2);
                 const size_t stride = (size_t)g.nodes;
                 atomicAdd(dst, 1ull);
@@ -201,16 +241,39 @@ __global__ __launch_bounds__(STPB) void k_sample_grid(const float4* __restrict__
 #pragma unroll
                 for (int f = 0; f < 5; ++f)
                     if (q.fields & (1 << f)) { atomicAdd(dst + (size_t)c * stride, (u64)sample_term(w, Aj[f])); ++c; }
+                if (GRAD) {
+                    float gr[3];
+                    sample_gradient(geom, Xj.w, q.k_w, gr);
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) { atomicAdd(dst + (size_t)c * stride, (u64)sample_weight_term(gr[b])); ++c; }
+#pragma unroll
+                    for (int f = 0; f < 5; ++f)
+                        if (gradients & (1 << f)) {
+#pragma unroll
+                            for (int b = 0; b < 3; ++b) { atomicAdd(dst + (size_t)c * stride, (u64)sample_term(gr[b], Aj[f])); ++c; }
+                        }
+                }
             }
         }
     }
 }
 
-// dynamic LDS: xyz [3][chunk] f32, then the partials [channels][chunk] i64, chunk = min(m, SP_CHUNK) rounded up to even
-__global__ __launch_bounds__(STPB) void k_sample_points(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
-                                                        int N, int tiles_per_block, SampleCommon q, const float* __restrict__ xyz, int m, int chunk,
-                                                        long long* __restrict__ planes) {
-    extern __shared__ __align__(16) unsigned char sample_lds[];
+__global__ __launch_bounds__(STPB) void k_sample_grid(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
+                                                      int N, int tiles_per_block, SampleCommon q, SampleGridDev g) {
+    sample_grid_body<false>(xm, vf, aux, N, tiles_per_block, q, g, 0);
+}
+
+__global__ __launch_bounds__(STPB) void k_sample_grid_grad(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
+                                                           int N, int tiles_per_block, SampleCommon q, SampleGridDev g, int gradients) {
+    sample_grid_body<true>(xm, vf, aux, N, tiles_per_block, q, g, gradients);
+}
+
+// dynamic LDS: the partials [channels][chunk] i64, then xyz [3][chunk] f32; chunk = min(m, SP_CHUNK) rounded up to even in the plain
+// instance, and in the gradient instance no more than fits SP_LDS_BYTES with q.channels channels (sample_points_chunk)
+template <bool GRAD>
+__device__ __forceinline__ void sample_points_body(unsigned char* sample_lds, const float4* __restrict__ xm, const float4* __restrict__ vf,
+                                                   const float4* __restrict__ aux, int N, int tiles_per_block, const SampleCommon& q,
+                                                   const float* __restrict__ xyz, int m, int chunk, long long* __restrict__ planes, int gradients) {
     u64* part = reinterpret_cast<u64*>(sample_lds);                       // [channels][chunk]
     float* P = reinterpret_cast<float*>(part + (size_t)q.channels * chunk);   // [3][chunk]
     const bool need_aux = (q.fields & (SPH_SAMPLE_DENSITY | SPH_SAMPLE_PRESSURE)) != 0;
@@ -235,13 +298,26 @@ __global__ __launch_bounds__(STPB) void k_sample_points(const float4* __restrict
             }
             for (int e = 0; e < cnt; ++e) {
                 float w;
-                if (!sample_pair(P[e], P[chunk + e], P[2 * chunk + e], X, q.inv_h, q.k_w, w)) continue;
+                SamplePairGeom geom;
+                if (!sample_pair(P[e], P[chunk + e], P[2 * chunk + e], X, q.inv_h, q.k_w, w, geom)) continue;
                 atomicAdd(part + e, 1ull);
                 atomicAdd(part + chunk + e, (u64)sample_weight_term(w));
                 int c = 2;
 #pragma unroll
                 for (int f = 0; f < 5; ++f)
                     if (q.fields & (1 << f)) { atomicAdd(part + (size_t)c * chunk + e, (u64)sample_term(w, A[f])); ++c; }
+                if (GRAD) {
+                    float gr[3];
+                    sample_gradient(geom, X.w, q.k_w, gr);
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) { atomicAdd(part + (size_t)c * chunk + e, (u64)sample_weight_term(gr[b])); ++c; }
+#pragma unroll
+                    for (int f = 0; f < 5; ++f)
+                        if (gradients & (1 << f)) {
+#pragma unroll
+                            for (int b = 0; b < 3; ++b) { atomicAdd(part + (size_t)c * chunk + e, (u64)sample_term(gr[b], A[f])); ++c; }
+                        }
+                }
             }
         }
         __syncthreads();
@@ -254,6 +330,20 @@ __global__ __launch_bounds__(STPB) void k_sample_points(const float4* __restrict
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(STPB) void k_sample_points(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
+                                                        int N, int tiles_per_block, SampleCommon q, const float* __restrict__ xyz, int m, int chunk,
+                                                        long long* __restrict__ planes) {
+    extern __shared__ __align__(16) unsigned char sample_lds[];
+    sample_points_body<false>(sample_lds, xm, vf, aux, N, tiles_per_block, q, xyz, m, chunk, planes, 0);
+}
+
+__global__ __launch_bounds__(STPB) void k_sample_points_grad(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
+                                                             int N, int tiles_per_block, SampleCommon q, const float* __restrict__ xyz, int m, int chunk,
+                                                             long long* __restrict__ planes, int gradients) {
+    extern __shared__ __align__(16) unsigned char sample_lds[];
+    sample_points_body<true>(sample_lds, xm, vf, aux, N, tiles_per_block, q, xyz, m, chunk, planes, gradients);
 }
 
 void sph_sample_release(SphContext* c) { sph_observe_release(c->sample, &SphSample::grid, &SphSample::pts_buf); }
@@ -292,6 +382,23 @@ static int sample_common(SphContext* c, const char* who, int32_t fields, const S
     return 0;
 }
 
+// the gradient mask of a gradient-carrying call: known bits, each of them also in `fields` (its planes need that field's sum).
+// Widens q->channels by Gx Gy Gz and three planes per bit.
+static int sample_gradients(SphContext* c, const char* who, int32_t gradients, SampleCommon* q) {
+    if (gradients & ~S_ALL_FIELDS) { snprintf(c->err, sizeof(c->err), "%s: gradients holds unknown bits", who); return SPH_E_INVALID; }
+    if (gradients & ~q->fields) {
+        snprintf(c->err, sizeof(c->err), "%s: gradients = %d names a plane that is not in fields = %d (the gradient needs that plane's sum)", who, gradients, q->fields);
+        return SPH_E_INVALID;
+    }
+    q->channels += 3 + 3 * __builtin_popcount((unsigned)gradients);
+    return 0;
+}
+
+static int sample_fail(SphContext* c, int rc, const char* who, const char* what) {
+    snprintf(c->err, sizeof(c->err), "%s: %s", who, what);
+    return rc;
+}
+
 static int sample_clear(SphContext* c, long long* p, size_t words) {
     size_t blocks = (words + STPB - 1) / STPB;
     if (blocks > 4096) blocks = 4096;
@@ -300,31 +407,32 @@ static int sample_clear(SphContext* c, long long* p, size_t words) {
     return 0;
 }
 
-extern "C" {
-
-int32_t sph_sample_grid(SphContext* c, const SphSampleGrid* p) {
-    static const char* who = "sph_sample_grid";
-    if (c && !p) return sph_fail(c, SPH_E_INVALID, "sph_sample_grid: the grid is NULL");
+// sph_sample_grid (with_grad false: `gradients` is not read) and sph_sample_grid_gradients
+static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad, int32_t gradients, const char* who) {
+    if (c && !p) return sample_fail(c, SPH_E_INVALID, who, "the grid is NULL");
     if (int rc = sph_observe_enter(c, who, " (its ghost records would be counted twice); fields are sampled on single-domain contexts only")) return rc;
     SampleCommon q;
     if (int rc = sample_common(c, who, p->fields, &p->select, p->inv_h, &q)) return rc;
+    const int n_fields = q.channels - 2;
+    if (with_grad)
+        if (int rc = sample_gradients(c, who, gradients, &q)) return rc;
     SampleGridDev g;
     g.h = 1.0f / p->inv_h;
-    if (!std::isfinite(g.h)) return sph_fail(c, SPH_E_INVALID, "sph_sample_grid: inv_h must be finite and positive (its reciprocal is not finite)");
+    if (!std::isfinite(g.h)) return sample_fail(c, SPH_E_INVALID, who, "inv_h must be finite and positive (its reciprocal is not finite)");
     long long nodes = 1;
     for (int a = 0; a < 3; ++a) {
-        if (p->n[a] < 1) return sph_fail(c, SPH_E_INVALID, "sph_sample_grid: n[a] must be at least 1");
+        if (p->n[a] < 1) return sample_fail(c, SPH_E_INVALID, who, "n[a] must be at least 1");
         nodes *= p->n[a];
         if (nodes > SPH_SAMPLE_MAX_NODES) {
-            snprintf(c->err, sizeof(c->err), "sph_sample_grid: %d x %d x %d nodes, a grid holds at most SPH_SAMPLE_MAX_NODES = %d", p->n[0], p->n[1], p->n[2], SPH_SAMPLE_MAX_NODES);
+            snprintf(c->err, sizeof(c->err), "%s: %d x %d x %d nodes, a grid holds at most SPH_SAMPLE_MAX_NODES = %d", who, p->n[0], p->n[1], p->n[2], SPH_SAMPLE_MAX_NODES);
             return SPH_E_INVALID;
         }
-        if (!std::isfinite(p->origin[a])) return sph_fail(c, SPH_E_INVALID, "sph_sample_grid: origin must be finite");
-        if (!std::isfinite(p->spacing[a]) || !(p->spacing[a] > 0.f)) return sph_fail(c, SPH_E_INVALID, "sph_sample_grid: spacing must be finite and positive");
+        if (!std::isfinite(p->origin[a])) return sample_fail(c, SPH_E_INVALID, who, "origin must be finite");
+        if (!std::isfinite(p->spacing[a]) || !(p->spacing[a] > 0.f)) return sample_fail(c, SPH_E_INVALID, who, "spacing must be finite and positive");
         // (the second clause: the footprints are built with 1 / inv_h, which is the support radius in every intended call)
         if (p->spacing[a] < c->p.support_radius / 8.f || p->spacing[a] * p->inv_h < 0.124f) {
-            snprintf(c->err, sizeof(c->err), "sph_sample_grid: spacing[%d] = %g is below an eighth of the support radius (%g): a particle's footprint is "
-                     "bounded at 17^3 nodes", a, (double)p->spacing[a], (double)(c->p.support_radius / 8.f));
+            snprintf(c->err, sizeof(c->err), "%s: spacing[%d] = %g is below an eighth of the support radius (%g): a particle's footprint is "
+                     "bounded at 17^3 nodes", who, a, (double)p->spacing[a], (double)(c->p.support_radius / 8.f));
             return SPH_E_INVALID;
         }
         g.n[a] = p->n[a]; g.origin[a] = p->origin[a]; g.spacing[a] = p->spacing[a]; g.inv_spacing[a] = 1.0f / p->spacing[a];
@@ -345,14 +453,52 @@ int32_t sph_sample_grid(SphContext* c, const SphSampleGrid* p) {
     const SphLive in = sph_live(c);
     if (in.N > 0) {
         const SphWalk w = sph_observe_walk(in.N, STPB, SG_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_sample_grid, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g);
+        if (with_grad)
+            hipLaunchKernelGGL(k_sample_grid_grad, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g, (int)gradients);
+        else
+            hipLaunchKernelGGL(k_sample_grid, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g);
         SPH_LAUNCH_CHECK(c);
     }
     s->grid_nodes = nodes;
     for (int a = 0; a < 3; ++a) { s->grid_n[a] = g.n[a]; s->grid_origin[a] = g.origin[a]; s->grid_spacing[a] = g.spacing[a]; }
-    s->grid_fields = q.channels - 2;
+    s->grid_fields = n_fields;
+    s->grid_grads = q.channels - 2 - n_fields;
     s->grid_have = true;
     return 0;
+}
+
+// the points the planes are cut into: what the plain instance always took, and for the gradient instance no more than fit its LDS budget
+static int sample_points_chunk(int m, int channels, bool with_grad) {
+    int cap = SP_CHUNK;
+    if (with_grad) {
+        cap = (int)(SP_LDS_BYTES / ((size_t)channels * 8 + 12)) & ~1;   // 25 channels: 164
+        if (cap > SP_CHUNK) cap = SP_CHUNK;
+    }
+    const int chunk = m < cap ? m : cap;
+    return (chunk + 1) & ~1;
+}
+
+extern "C" {
+
+int32_t sph_sample_grid(SphContext* c, const SphSampleGrid* p) { return sample_grid_run(c, p, false, 0, "sph_sample_grid"); }
+
+int32_t sph_sample_grid_gradients(SphContext* c, const SphSampleGrid* p, int32_t gradients) {
+    return sample_grid_run(c, p, true, gradients, "sph_sample_grid_gradients");
+}
+
+int32_t sph_sample_grid_gradients_download(SphContext* c, int64_t* grads, int64_t nodes) {
+    if (!c) return SPH_E_INVALID;
+    const SphSample* s = c->sample;
+    if (!s || !s->grid_have) return sph_fail(c, SPH_E_STATE, "sph_sample_grid_gradients_download: nothing has been sampled (call sph_sample_grid_gradients first)");
+    if (s->grid_grads == 0) return sph_fail(c, SPH_E_STATE, "sph_sample_grid_gradients_download: the last grid was sampled without gradients (call sph_sample_grid_gradients)");
+    if (nodes != s->grid_nodes) {
+        snprintf(c->err, sizeof(c->err), "sph_sample_grid_gradients_download: nodes = %lld, the last grid has %lld nodes", (long long)nodes, s->grid_nodes);
+        return SPH_E_INVALID;
+    }
+    SPH_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)s->grid_nodes;
+    if (grads) SPH_HIP(c, hipMemcpyAsync(grads, s->grid + (size_t)(2 + s->grid_fields) * n, (size_t)s->grid_grads * n * 8, hipMemcpyDeviceToHost, c->stream));
+    return sph_observe_download(c, nullptr, nullptr, 0);
 }
 
 int32_t sph_sample_grid_download(SphContext* c, int64_t* weight, int64_t* count, int64_t* sums, int64_t nodes) {
@@ -371,22 +517,28 @@ int32_t sph_sample_grid_download(SphContext* c, int64_t* weight, int64_t* count,
     return sph_observe_download(c, nullptr, nullptr, 0);
 }
 
-int32_t sph_sample_points(SphContext* c, const float* xyz, int32_t m, int32_t fields, const SphSampleSelect* select, float inv_h) {
-    static const char* who = "sph_sample_points";
-    if (c && !xyz) return sph_fail(c, SPH_E_INVALID, "sph_sample_points: xyz is NULL");
+}  // extern "C"
+
+// sph_sample_points (with_grad false: `gradients` is not read) and sph_sample_points_gradients
+static int sample_points_run(SphContext* c, const float* xyz, int32_t m, int32_t fields, bool with_grad, int32_t gradients,
+                             const SphSampleSelect* select, float inv_h, const char* who) {
+    if (c && !xyz) return sample_fail(c, SPH_E_INVALID, who, "xyz is NULL");
     if (int rc = sph_observe_enter(c, who, " (its ghost records would be counted twice); fields are sampled on single-domain contexts only")) return rc;
     SampleCommon q;
     if (int rc = sample_common(c, who, fields, select, inv_h, &q)) return rc;
+    const int n_fields = q.channels - 2;
+    if (with_grad)
+        if (int rc = sample_gradients(c, who, gradients, &q)) return rc;
     if (m < 1 || m > SPH_SAMPLE_MAX_POINTS) {
-        snprintf(c->err, sizeof(c->err), "sph_sample_points: m = %d, must be in [1, SPH_SAMPLE_MAX_POINTS = %d]", m, SPH_SAMPLE_MAX_POINTS);
+        snprintf(c->err, sizeof(c->err), "%s: m = %d, must be in [1, SPH_SAMPLE_MAX_POINTS = %d]", who, m, SPH_SAMPLE_MAX_POINTS);
         return SPH_E_INVALID;
     }
     for (int k = 0; k < 3 * m; ++k)
-        if (!std::isfinite(xyz[k])) return sph_fail(c, SPH_E_INVALID, "sph_sample_points: a point is not finite");
+        if (!std::isfinite(xyz[k])) return sample_fail(c, SPH_E_INVALID, who, "a point is not finite");
     if (int rc = sample_state(c, who)) return rc;
     SphSample* s = c->sample;
     if (!s->pts_buf) {
-        const size_t bytes = (size_t)3 * SPH_SAMPLE_MAX_POINTS * 4 + (size_t)SG_MAX_CHANNELS * SPH_SAMPLE_MAX_POINTS * 8;
+        const size_t bytes = (size_t)3 * SPH_SAMPLE_MAX_POINTS * 4 + (size_t)(SG_MAX_CHANNELS + SG_MAX_GRAD_CHANNELS) * SPH_SAMPLE_MAX_POINTS * 8;
         if (int rc = sph_observe_alloc(c, &s->pts_buf, bytes, who, "the points and their planes")) return rc;
         s->pts = (long long*)((char*)s->pts_buf + (size_t)3 * SPH_SAMPLE_MAX_POINTS * 4);
     }
@@ -400,17 +552,49 @@ int32_t sph_sample_points(SphContext* c, const float* xyz, int32_t m, int32_t fi
     const SphLive in = sph_live(c);
     if (in.N > 0) {
         const SphWalk w = sph_observe_walk(in.N, STPB, SP_MAX_BLOCKS);
-        int chunk = m < SP_CHUNK ? m : SP_CHUNK;
-        chunk = (chunk + 1) & ~1;
+        const int chunk = sample_points_chunk(m, q.channels, with_grad);
         const size_t lds = (size_t)chunk * ((size_t)q.channels * 8 + 12);   // <= 512 * 68 B = 34,816 B
-        hipLaunchKernelGGL(k_sample_points, dim3(w.blocks), dim3(STPB), lds, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q,
-                           (const float*)s->pts_buf, m, chunk, s->pts);
+        if (with_grad)
+            hipLaunchKernelGGL(k_sample_points_grad, dim3(w.blocks), dim3(STPB), lds, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q,
+                               (const float*)s->pts_buf, m, chunk, s->pts, (int)gradients);
+        else
+            hipLaunchKernelGGL(k_sample_points, dim3(w.blocks), dim3(STPB), lds, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q,
+                               (const float*)s->pts_buf, m, chunk, s->pts);
         SPH_LAUNCH_CHECK(c);
     }
     s->pts_m = m;
-    s->pts_fields = q.channels - 2;
+    s->pts_fields = n_fields;
+    s->pts_grads = q.channels - 2 - n_fields;
     s->pts_have = true;
     return 0;
+}
+
+extern "C" {
+
+int32_t sph_sample_points(SphContext* c, const float* xyz, int32_t m, int32_t fields, const SphSampleSelect* select, float inv_h) {
+    return sample_points_run(c, xyz, m, fields, false, 0, select, inv_h, "sph_sample_points");
+}
+
+int32_t sph_sample_points_gradients(SphContext* c, const float* xyz, int32_t m, int32_t fields, int32_t gradients, const SphSampleSelect* select,
+                                    float inv_h) {
+    return sample_points_run(c, xyz, m, fields, true, gradients, select, inv_h, "sph_sample_points_gradients");
+}
+
+int32_t sph_sample_points_gradients_download(SphContext* c, int64_t* grads, int32_t m) {
+    if (!c) return SPH_E_INVALID;
+    SphSample* s = c->sample;
+    if (!s || !s->pts_have) return sph_fail(c, SPH_E_STATE, "sph_sample_points_gradients_download: nothing has been sampled (call sph_sample_points_gradients first)");
+    if (s->pts_grads == 0) return sph_fail(c, SPH_E_STATE, "sph_sample_points_gradients_download: the last points were sampled without gradients (call sph_sample_points_gradients)");
+    if (m != s->pts_m) {
+        snprintf(c->err, sizeof(c->err), "sph_sample_points_gradients_download: m = %d, the last points call took %d points", m, s->pts_m);
+        return SPH_E_INVALID;
+    }
+    SPH_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)s->pts_m;
+    if (grads) SPH_HIP(c, hipMemcpyAsync(grads, s->pts + (size_t)(2 + s->pts_fields) * n, (size_t)s->pts_grads * n * 8, hipMemcpyDeviceToHost, c->stream));
+    const int rc = sph_observe_download(c, nullptr, nullptr, 0);
+    if (rc <= 0) s->pts_copying = false;   // the stream has drained: the host copy of the points is free again
+    return rc;
 }
 
 int32_t sph_sample_points_download(SphContext* c, int64_t* weight, int64_t* count, int64_t* sums, int32_t m) {

@@ -434,7 +434,7 @@ class ParticleSystem:
         from . import export as _export
         return _export.export(self, objects=objects, material=material, fields=fields, box=box, every=every, phase=phase)
 
-    def sample_grid(self, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None):
+    def sample_grid(self, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None, gradients=()):
         """The SPH interpolation of `fields` (names from velocity, density, pressure) at the nodes origin + k * spacing of a
         regular grid (sample.FieldGrid: raw i64 planes `weight`, `count`, `sums`; `fill`, `velocity`, `density`, `pressure`,
         `wet()` follow from them; `write_vtk(path)`).  `spacing` (one number or one per axis) defaults to the particle
@@ -442,15 +442,20 @@ class ParticleSystem:
         "fluid" (default), "solid", an id or None (any; solids then contribute with their boundary volumes); `objects`: ids to
         keep (None: all).  x and v are the current values; density and pressure are those of the last step's density sweep,
         one dt behind.  One streaming pass on the device behind whatever was enqueued; only the planes are copied back
-        (synchronises).  Reads the records; changes nothing a later step reads."""
+        (synchronises).  Reads the records; changes nothing a later step reads.
+        `gradients`: names from `fields` whose analytic gradient the same pass sums as well, or ("fill",) for the fill gradient
+        alone, which comes with any of them (raw `grad_fill`, `grad_sums`; `fill_gradient`, `surface_normal`,
+        `velocity_gradient`, `vorticity`, `divergence`, `strain_rate`, `q_criterion`, `pressure_gradient`, `density_gradient`).
+        () is the call as it was."""
         from . import sample as _sample
-        return _sample.sample_grid(self, spacing=spacing, origin=origin, shape=shape, fields=fields, material=material, objects=objects)
+        return _sample.sample_grid(self, spacing=spacing, origin=origin, shape=shape, fields=fields, material=material, objects=objects,
+                                   gradients=gradients)
 
-    def sample_points(self, points, fields=("velocity",), material="fluid", objects=None):
+    def sample_points(self, points, fields=("velocity",), material="fluid", objects=None, gradients=()):
         """The same interpolation at up to 1024 probe points [[x, y, z], ...] (sample.FieldProbes: the same planes and views per
-        point, `rows()` for JSON)."""
+        point, `rows()` for JSON); `gradients` as for `sample_grid`."""
         from . import sample as _sample
-        return _sample.sample_points(self, points, fields=fields, material=material, objects=objects)
+        return _sample.sample_points(self, points, fields=fields, material=material, objects=objects, gradients=gradients)
 
     def surface_mesh(self, spacing=None, origin=None, shape=None, iso=0.4, cap=True, material="fluid", objects=None):
         """The surface of the selected particles as an indexed triangle mesh (mesh.SurfaceMesh: `vertices`, `normals`,

@@ -35,7 +35,8 @@ defaults of render.SurfaceStyle.  Absent or "spheres": the frames are what they 
 carries field, lo, hi and colormap as tEXt chunks, and the final report holds `frame_colour_range`, the range of the last frame.
 A Configuration with "sampleGrid": {"spacing": s, "origin": [..], "shape": [..], "fields": ["velocity", "pressure"], "objects": [0]}
 (every key optional) writes `{scene}_output/grid_{cnt:06}.vtk` per exported interval: the fluid's fields interpolated on a regular
-grid on the device (sample.py), a legacy binary STRUCTURED_POINTS volume.  "probes": {"points": [[x, y, z], ...], "fields": [...]}
+grid on the device (sample.py), a legacy binary STRUCTURED_POINTS volume ("gradients": ["velocity"] adds vorticity, divergence, Q and the fill gradient;
+the same key in "probes" adds them to the rows).  "probes": {"points": [[x, y, z], ...], "fields": [...]}
 with `--probes PATH` writes one JSON line per exported interval: frame, time and one row per point (count, fill, the fields).
 Without the keys nothing changes.
 A Configuration with "exportMesh": {"spacing": s, "origin": [..], "shape": [..], "iso": 0.4, "cap": true, "objects": [0]} (every key

@@ -5,7 +5,10 @@ The SPH interpolation of velocity, density and pressure at places: the nodes of 
 shape has a 1 in it) or a handful of probe points.  One streaming pass on the device in which every selected particle adds its
 kernel-weighted share to the sample positions inside its support radius; only the planes cross to the host.  The raw planes are
 i64 fixed-point sums (scale 2^30): `weight` = sum of w, `sums[f]` = sum of w * A_f, `count` = number of contributing particles;
-a value is sums[f] / weight.  Nothing in this module touches the GPU when it is imported: the library is reached through the
+a value is sums[f] / weight.  With `gradients=` the same pass also sums the kernel-gradient terms (section "Field sampling:
+gradients"): `grad_fill` = sum of h grad w, `grad_sums[f]` = sum of h grad w * A_f, from which the analytic gradient of the
+interpolant follows, grad A = inv_h (grad_sums[f] - A grad_fill) / weight, and with it vorticity, divergence, strain rate, the
+Q-criterion, the pressure gradient and the free-surface normal.  Nothing in this module touches the GPU when it is imported: the library is reached through the
 ParticleSystem handed to `sample_grid` / `sample_points`.
 """
 from __future__ import annotations
@@ -20,8 +23,9 @@ MAX_NODES, MAX_POINTS, MAX_OBJECTS = 1 << 24, 1024, 32
 FIELD_PLANES = {"velocity": ("vx", "vy", "vz"), "density": ("density",), "pressure": ("pressure",)}
 PLANE_BITS = {"vx": 1, "vy": 2, "vz": 4, "density": 8, "pressure": 16}
 MATERIALS = {"solid": 0, "fluid": 1}
-GRID_CONFIG_KEYS = ("spacing", "origin", "shape", "fields", "objects")
-PROBES_CONFIG_KEYS = ("points", "fields")
+GRID_CONFIG_KEYS = ("spacing", "origin", "shape", "fields", "objects", "gradients")
+PROBES_CONFIG_KEYS = ("points", "fields", "gradients")
+FILL = "fill"                        # the one name `gradients` takes beside those of FIELD_PLANES: the fill gradient alone
 
 
 def _integer(value, name) -> int:
@@ -87,6 +91,30 @@ def select_args(fields=("velocity",), material="fluid", objects=None) -> dict:
     return {"fields": names, "planes": planes, "mask": mask, "material": mat, "objects": ids}
 
 
+def gradient_args(gradients=(), fields=("velocity",)) -> dict:
+    """The `gradients` argument of `sample_grid` / `sample_points`, checked without a context against the (checked) `fields`:
+    {"names": field names in plane order, "planes": the planes whose gradient sums are asked for, "mask", "any": whether the
+    gradient-carrying entry is called at all}.  The fill gradient comes with any non-empty `gradients`; ("fill",) asks for it
+    alone.  ValueError for one string, an unknown name, a name given twice and a name that is not in `fields`."""
+    if isinstance(gradients, str):
+        raise ValueError("gradients must be a sequence of names, not one string")
+    gradients = list(gradients)
+    unknown = [g for g in gradients if g != FILL and g not in FIELD_PLANES]
+    if unknown:
+        raise ValueError(f"unknown gradient(s) {unknown}: choose from {list(FIELD_PLANES) + [FILL]}")
+    if len(set(gradients)) != len(gradients):
+        raise ValueError("a gradient is named twice")
+    missing = [g for g in gradients if g != FILL and g not in fields]
+    if missing:
+        raise ValueError(f"the gradient of {missing} needs that field's sums: name it in fields as well")
+    names = tuple(n for n in FIELD_PLANES if n in gradients)
+    planes = tuple(p for n in names for p in FIELD_PLANES[n])
+    mask = 0
+    for p in planes:
+        mask |= PLANE_BITS[p]
+    return {"names": names, "planes": planes, "mask": mask, "any": bool(gradients)}
+
+
 def grid_args(spacing=None, origin=None, shape=None, *, particle_diameter, domain_size) -> dict:
     """Defaults resolved: spacing = the particle diameter (one number: all three axes), origin = 0, shape = the nodes that
     cover the domain from the origin, ceil((domain_size - origin) / spacing) + 1 per axis.  Returns {"spacing", "origin"
@@ -139,15 +167,27 @@ def node_positions(origin, spacing, shape) -> np.ndarray:
 
 class _Sampled:
     """The raw planes over any shape -- `weight`, `count` i64 [...], `sums` i64 [F, ...] with F = len(planes) -- and the f64
-    views that follow from them."""
+    views that follow from them.  A sample that carried gradients also has `grad_fill` i64 [3, ...], `grad_sums` i64
+    [Fg, 3, ...] with Fg = len(grad_planes), and `inv_h`, the factor that gives the dimensionless sums their 1 / length; without
+    gradients `grad_fill` is None and `grad_sums` is empty."""
 
-    def __init__(self, weight, count, sums, planes, time):
+    def __init__(self, weight, count, sums, planes, time, grad_fill=None, grad_sums=None, grad_planes=(), inv_h=None):
         self.weight = np.asarray(weight, dtype=np.int64)
         self.count = np.asarray(count, dtype=np.int64).reshape(self.weight.shape)
         self.planes = tuple(planes)
         self.sums = np.asarray(sums, dtype=np.int64).reshape((len(self.planes),) + self.weight.shape)
         self.fields = tuple(n for n in FIELD_PLANES if all(p in self.planes for p in FIELD_PLANES[n]))
         self.time = float(time)
+        self.grad_planes = tuple(grad_planes) if grad_fill is not None else ()
+        if any(p not in self.planes for p in self.grad_planes):
+            raise ValueError("a gradient plane needs the sums of that plane")
+        self.grad_fill = None if grad_fill is None else np.asarray(grad_fill, dtype=np.int64).reshape((3,) + self.weight.shape)
+        self.grad_sums = (np.zeros((0, 3) + self.weight.shape, dtype=np.int64) if grad_fill is None or grad_sums is None else
+                          np.asarray(grad_sums, dtype=np.int64).reshape((len(self.grad_planes), 3) + self.weight.shape))
+        self.gradients = tuple(n for n in FIELD_PLANES if all(p in self.grad_planes for p in FIELD_PLANES[n]))
+        if grad_fill is not None and inv_h is None:
+            raise ValueError("gradient sums need inv_h")
+        self.inv_h = None if inv_h is None else float(inv_h)
 
     @property
     def fill(self):
@@ -177,16 +217,97 @@ class _Sampled:
     def pressure(self):
         return self._value("pressure")
 
+    # ---- gradients: every view is f64 and NaN where weight == 0 ----
+    def _no_gradient(self, what):
+        return ValueError(f"the gradient of {what} was not sampled: the gradients are {list(self.gradients) + ([FILL] if self.grad_fill is not None else [])}")
+
+    @property
+    def fill_gradient(self):
+        """[..., 3] f64: inv_h * grad_fill / 2^30, the gradient of `fill` (it points into the fluid)."""
+        if self.grad_fill is None:
+            raise self._no_gradient(FILL)
+        g = np.moveaxis(self.grad_fill.astype(np.float64), 0, -1) * (self.inv_h / float(1 << SCALE_LOG2))
+        return np.where((self.weight != 0)[..., None], g, np.nan)
+
+    @property
+    def surface_normal(self):
+        """[..., 3] f64: -fill_gradient / |fill_gradient|, out of the fluid; NaN where that length is 0."""
+        g = self.fill_gradient
+        length = np.sqrt((g * g).sum(axis=-1))
+        ok = length > 0
+        return np.where(ok[..., None], -g / np.where(ok, length, 1.0)[..., None], np.nan)
+
+    def _gradient(self, plane):
+        """[..., 3] f64: inv_h * (grad_sums[f] - A grad_fill) / weight, the gradient of the interpolant A = sums[f] / weight."""
+        if plane not in self.grad_planes:
+            raise self._no_gradient(plane)
+        has = self.weight != 0
+        w = np.where(has, self.weight, 1).astype(np.float64)
+        a = self.sums[self.planes.index(plane)].astype(np.float64) / w
+        s = self.grad_sums[self.grad_planes.index(plane)].astype(np.float64)
+        g = (s - a[None] * self.grad_fill.astype(np.float64)) / w[None] * self.inv_h
+        return np.where(has[..., None], np.moveaxis(g, 0, -1), np.nan)
+
+    @property
+    def velocity_gradient(self):
+        """[..., 3, 3] f64, (component, axis): velocity_gradient[..., c, a] = d v_c / d x_a."""
+        return np.stack([self._gradient(p) for p in FIELD_PLANES["velocity"]], axis=-2)
+
+    @property
+    def density_gradient(self):
+        return self._gradient("density")
+
+    @property
+    def pressure_gradient(self):
+        return self._gradient("pressure")
+
+    @property
+    def vorticity(self):
+        """[..., 3] f64: curl v."""
+        j = self.velocity_gradient
+        return np.stack([j[..., 2, 1] - j[..., 1, 2], j[..., 0, 2] - j[..., 2, 0], j[..., 1, 0] - j[..., 0, 1]], axis=-1)
+
+    @property
+    def divergence(self):
+        j = self.velocity_gradient
+        return j[..., 0, 0] + j[..., 1, 1] + j[..., 2, 2]
+
+    @property
+    def strain_rate(self):
+        """The Frobenius norm of the symmetric part S = (J + J^T) / 2 of the velocity gradient."""
+        j = self.velocity_gradient
+        s = 0.5 * (j + np.swapaxes(j, -1, -2))
+        return np.sqrt((s * s).sum(axis=(-1, -2)))
+
+    @property
+    def q_criterion(self):
+        """(|Omega|^2 - |S|^2) / 2 with Omega = (J - J^T) / 2: positive where rotation dominates strain."""
+        j = self.velocity_gradient
+        s, o = 0.5 * (j + np.swapaxes(j, -1, -2)), 0.5 * (j - np.swapaxes(j, -1, -2))
+        return 0.5 * ((o * o).sum(axis=(-1, -2)) - (s * s).sum(axis=(-1, -2)))
+
+    def gradient_views(self):
+        """(name, f64 array) of the derived gradient fields that were sampled, in the order the VTK writer and `rows()` use."""
+        out = []
+        if self.grad_fill is not None:
+            out.append(("fill_gradient", self.fill_gradient))
+        if "velocity" in self.gradients:
+            out += [("vorticity", self.vorticity), ("divergence", self.divergence), ("q_criterion", self.q_criterion)]
+        for name in ("pressure", "density"):
+            if name in self.gradients:
+                out.append((f"{name}_gradient", self._gradient(name)))
+        return out
+
 
 class FieldGrid(_Sampled):
     """One sampled grid: the raw planes [n0, n1, n2] plus `time`, `origin`, `spacing`, `shape`; `fill`, `velocity`, `density`,
     `pressure`, `wet()` as f64 views; `write_vtk(path)`.  Node (k0, k1, k2) is at origin + k * spacing."""
 
-    def __init__(self, weight, count, sums, planes, *, time, origin, spacing, shape):
+    def __init__(self, weight, count, sums, planes, *, time, origin, spacing, shape, grad_fill=None, grad_sums=None, grad_planes=(), inv_h=None):
         self.shape = tuple(int(n) for n in shape)
         if len(self.shape) != 3:
             raise ValueError("shape must be three node counts")
-        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.shape), count, sums, planes, time)
+        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.shape), count, sums, planes, time, grad_fill, grad_sums, grad_planes, inv_h)
         self.origin = _triple(origin, "origin")
         self.spacing = _triple(spacing, "spacing")
 
@@ -195,12 +316,15 @@ class FieldGrid(_Sampled):
         return node_positions(self.origin, self.spacing, self.shape)
 
     def vtk_arrays(self):
-        """(name, components, f32 array in VTK point order: x fastest) of what `write_vtk` writes: fill, then the fields."""
+        """(name, components, f32 array in VTK point order: x fastest) of what `write_vtk` writes: fill, then the fields, then
+        the gradient fields of a sample that carried gradients (`gradient_views`)."""
         order = lambda a: np.ascontiguousarray(np.transpose(a, (2, 1, 0) + tuple(range(3, a.ndim))))
         out = [("fill", 1, order(self.fill).astype(np.float32))]
         for name in self.fields:
             a = getattr(self, name)
             out.append((name, 3 if name == "velocity" else 1, order(a).astype(np.float32)))
+        for name, a in self.gradient_views():
+            out.append((name, 3 if a.ndim == 4 else 1, order(a).astype(np.float32)))
         return out
 
     def write_vtk(self, path):
@@ -224,35 +348,39 @@ class FieldGrid(_Sampled):
 class FieldProbes(_Sampled):
     """The same views per probe point: raw planes [m], `points` f32 [m, 3]; `rows()` for JSON."""
 
-    def __init__(self, points, weight, count, sums, planes, *, time):
+    def __init__(self, points, weight, count, sums, planes, *, time, grad_fill=None, grad_sums=None, grad_planes=(), inv_h=None):
         self.points = np.asarray(points, dtype=np.float32).reshape(-1, 3)
-        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.points.shape[0]), count, sums, planes, time)
+        super().__init__(np.asarray(weight, dtype=np.int64).reshape(self.points.shape[0]), count, sums, planes, time, grad_fill, grad_sums,
+                         grad_planes, inv_h)
 
     def rows(self):
-        """One JSON-ready dict per point: point, count, fill and the sampled fields (None where nothing contributed)."""
+        """One JSON-ready dict per point: point, count, fill, the sampled fields and the gradient fields of `gradient_views`
+        (None where nothing contributed)."""
         num = lambda v: None if math.isnan(v) else float(v)
         views = {name: getattr(self, name) for name in self.fields}
+        views.update(self.gradient_views())
         fill = self.fill
         out = []
         for k in range(self.points.shape[0]):
             row = {"point": [float(v) for v in self.points[k]], "count": int(self.count[k]), "fill": float(fill[k])}
             for name, a in views.items():
-                row[name] = [num(v) for v in a[k]] if name == "velocity" else num(a[k])
+                row[name] = [num(v) for v in a[k]] if a.ndim == 2 else num(a[k])
             out.append(row)
         return out
 
 
-def _fields_from_spec(spec, key, default):
-    fields = spec.get("fields", default)
+def _fields_from_spec(spec, key, default, name="fields"):
+    fields = spec.get(name, default)
     if isinstance(fields, str) or not isinstance(fields, (list, tuple)):
-        raise ValueError(f'"{key}": fields must be a list of names')
+        raise ValueError(f'"{key}": {name} must be a list of names')
     return tuple(fields)
 
 
 def sample_grid_config(config):
-    """The scene's "sampleGrid" object: {"spacing": s, "origin": [..], "shape": [..], "fields": [..], "objects": [..]}, every key
-    optional ({} = velocity on the default grid).  Returns the keyword arguments of `sample_grid`, or None when the key is
-    absent.  A misspelt key or a bad value raises ValueError."""
+    """The scene's "sampleGrid" object: {"spacing": s, "origin": [..], "shape": [..], "fields": [..], "objects": [..],
+    "gradients": [..]}, every key optional ({} = velocity on the default grid).  Returns the keyword arguments of `sample_grid`
+    ("gradients" among them only when the scene names it), or None when the key is absent.  A misspelt key or a bad value
+    raises ValueError."""
     spec = config.get_cfg("sampleGrid")
     if spec is None:
         return None
@@ -263,8 +391,11 @@ def sample_grid_config(config):
         raise ValueError(f'"sampleGrid": unknown key(s) {sorted(unknown)}')
     kw = {"spacing": spec.get("spacing"), "origin": spec.get("origin"), "shape": spec.get("shape"),
           "fields": _fields_from_spec(spec, "sampleGrid", ("velocity",)), "objects": spec.get("objects")}
+    if "gradients" in spec:
+        kw["gradients"] = _fields_from_spec(spec, "sampleGrid", (), "gradients")
     try:
-        select_args(fields=kw["fields"], objects=kw["objects"])
+        sel = select_args(fields=kw["fields"], objects=kw["objects"])
+        gradient_args(kw.get("gradients", ()), sel["fields"])
         grid_args(kw["spacing"], kw["origin"], kw["shape"], particle_diameter=1.0, domain_size=(1.0, 1.0, 1.0))
     except ValueError as e:
         raise ValueError(f'"sampleGrid": {e}') from e
@@ -272,8 +403,9 @@ def sample_grid_config(config):
 
 
 def probes_config(config):
-    """The scene's "probes" object: {"points": [[x, y, z], ...], "fields": [..]}.  Returns the keyword arguments of
-    `sample_points`, or None when the key is absent.  A misspelt key or a bad value raises ValueError."""
+    """The scene's "probes" object: {"points": [[x, y, z], ...], "fields": [..], "gradients": [..]}.  Returns the keyword
+    arguments of `sample_points` ("gradients" among them only when the scene names it), or None when the key is absent.  A
+    misspelt key or a bad value raises ValueError."""
     spec = config.get_cfg("probes")
     if spec is None:
         return None
@@ -287,10 +419,14 @@ def probes_config(config):
     try:
         pts = points_arg(spec["points"])
         fields = _fields_from_spec(spec, "probes", ("velocity",))
-        select_args(fields=fields)
+        sel = select_args(fields=fields)
+        kw = {"points": pts.astype(np.float64).tolist(), "fields": fields}
+        if "gradients" in spec:
+            kw["gradients"] = _fields_from_spec(spec, "probes", (), "gradients")
+            gradient_args(kw["gradients"], sel["fields"])
     except ValueError as e:
         raise ValueError(f'"probes": {e}') from e
-    return {"points": pts.astype(np.float64).tolist(), "fields": fields}
+    return kw
 
 
 def inv_h_f32(support_radius) -> float:
@@ -308,16 +444,31 @@ def make_select(args: dict):
     return s
 
 
-def download_grid_raw(ps, grid, n_planes):
-    """sph_sample_grid + sph_sample_grid_download: (weight, count, sums) as flat i64 arrays (synchronises)."""
+def download_grid_raw(ps, grid, n_planes, gradients=None):
+    """sph_sample_grid + sph_sample_grid_download: (weight, count, sums) as flat i64 arrays (synchronises).  With `gradients`
+    (a mask of plane bits; 0 = the fill gradient alone) the gradient-carrying entry is called instead and the gradient planes
+    [3 + 3 Fg, nodes] come fourth."""
     import ctypes as C
-    ps._call("sph_sample_grid", C.byref(grid))
+    if gradients is None:
+        ps._call("sph_sample_grid", C.byref(grid))
+    else:
+        ps._call("sph_sample_grid_gradients", C.byref(grid), int(gradients))
     nodes = int(grid.n[0]) * int(grid.n[1]) * int(grid.n[2])
     weight, count = np.empty(nodes, dtype=np.int64), np.empty(nodes, dtype=np.int64)
     sums = np.empty((n_planes, nodes), dtype=np.int64)
     ps._call("sph_sample_grid_download", weight.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
              sums.ctypes.data_as(C.c_void_p) if n_planes else None, nodes)
-    return weight, count, sums
+    if gradients is None:
+        return weight, count, sums
+    grads = np.empty((3 + 3 * bin(int(gradients)).count("1"), nodes), dtype=np.int64)
+    ps._call("sph_sample_grid_gradients_download", grads.ctypes.data_as(C.c_void_p), nodes)
+    return weight, count, sums, grads
+
+
+def _gradient_kw(ps, grads, ga) -> dict:
+    """The gradient arguments of FieldGrid / FieldProbes from the downloaded planes [3 + 3 Fg, ...]."""
+    return {"grad_fill": grads[:3], "grad_sums": grads[3:].reshape((len(ga["planes"]), 3) + grads.shape[1:]), "grad_planes": ga["planes"],
+            "inv_h": inv_h_f32(ps.support_radius)}
 
 
 def _refuse_slab(ps):
@@ -326,30 +477,43 @@ def _refuse_slab(ps):
                                   "counted twice (the planes of the ranks' owned ranges would have to be all-reduced)")
 
 
-def sample_grid(ps, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None) -> FieldGrid:
+def sample_grid(ps, spacing=None, origin=None, shape=None, fields=("velocity",), material="fluid", objects=None, gradients=()) -> FieldGrid:
     import ctypes as C
     from . import _lib
     sel = select_args(fields=fields, material=material, objects=objects)
+    gr = gradient_args(gradients, sel["fields"])
     ga = grid_args(spacing, origin, shape, particle_diameter=ps.particle_diameter, domain_size=ps.domain_size)
     _refuse_slab(ps)
     g = _lib.SphSampleGrid()
     g.n = (C.c_int32 * 3)(*ga["shape"])
     g.origin, g.spacing = (C.c_float * 3)(*ga["origin"]), (C.c_float * 3)(*ga["spacing"])
     g.inv_h, g.fields, g.select = inv_h_f32(ps.support_radius), sel["mask"], make_select(sel)
-    weight, count, sums = download_grid_raw(ps, g, len(sel["planes"]))
-    return FieldGrid(weight, count, sums, sel["planes"], time=ps.time, origin=ga["origin"], spacing=ga["spacing"], shape=ga["shape"])
+    if not gr["any"]:
+        weight, count, sums = download_grid_raw(ps, g, len(sel["planes"]))
+        return FieldGrid(weight, count, sums, sel["planes"], time=ps.time, origin=ga["origin"], spacing=ga["spacing"], shape=ga["shape"])
+    weight, count, sums, grads = download_grid_raw(ps, g, len(sel["planes"]), gr["mask"])
+    return FieldGrid(weight, count, sums, sel["planes"], time=ps.time, origin=ga["origin"], spacing=ga["spacing"], shape=ga["shape"],
+                     **_gradient_kw(ps, grads, gr))
 
 
-def sample_points(ps, points, fields=("velocity",), material="fluid", objects=None) -> FieldProbes:
+def sample_points(ps, points, fields=("velocity",), material="fluid", objects=None, gradients=()) -> FieldProbes:
     import ctypes as C
     sel = select_args(fields=fields, material=material, objects=objects)
+    gr = gradient_args(gradients, sel["fields"])
     pts = points_arg(points)
     _refuse_slab(ps)
     m, n_planes = pts.shape[0], len(sel["planes"])
     s = make_select(sel)
-    ps._call("sph_sample_points", pts.ctypes.data_as(C.c_void_p), m, sel["mask"], C.byref(s), inv_h_f32(ps.support_radius))
+    if gr["any"]:
+        ps._call("sph_sample_points_gradients", pts.ctypes.data_as(C.c_void_p), m, sel["mask"], gr["mask"], C.byref(s), inv_h_f32(ps.support_radius))
+    else:
+        ps._call("sph_sample_points", pts.ctypes.data_as(C.c_void_p), m, sel["mask"], C.byref(s), inv_h_f32(ps.support_radius))
     weight, count = np.empty(m, dtype=np.int64), np.empty(m, dtype=np.int64)
     sums = np.empty((n_planes, m), dtype=np.int64)
     ps._call("sph_sample_points_download", weight.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
              sums.ctypes.data_as(C.c_void_p) if n_planes else None, m)
-    return FieldProbes(pts, weight, count, sums, sel["planes"], time=ps.time)
+    if not gr["any"]:
+        return FieldProbes(pts, weight, count, sums, sel["planes"], time=ps.time)
+    grads = np.empty((3 + 3 * len(gr["planes"]), m), dtype=np.int64)
+    ps._call("sph_sample_points_gradients_download", grads.ctypes.data_as(C.c_void_p), m)
+    return FieldProbes(pts, weight, count, sums, sel["planes"], time=ps.time, **_gradient_kw(ps, grads, gr))
