@@ -930,6 +930,72 @@ int32_t sph_mesh_counts(SphContext* ctx, int64_t* vertices, int64_t* triangles);
 int32_t sph_mesh_download(SphContext* ctx, float* pos /*[V][3]*/, float* nrm /*[V][3]*/, int32_t* tri /*[T][3]*/,
                           int64_t vertices, int64_t triangles);         /* any pointer may be NULL; synchronises */
 
+/* ======================================================================================
+ * Passive tracers (the reference has none; every observer above is Eulerian): a context may hold ONE set of m tracers,
+ * 0 <= m <= SPH_TRACERS_MAX: massless points that follow the flow, for pathlines, streaklines, dye and residence times.  No sweep
+ * ever sees them and nothing of the particle state is written for them.
+ * THE HOOK: while a set is registered, every step of sph_step / sph_dfsph_step advances it by ONE forward-Euler step with the state
+ * at the BEGINNING of that step.  The advance is enqueued right behind the step's sort, before the step's sweeps: there the current
+ * cell array (the inclusive prefix over the G cells) describes exactly the positions of the sorted records, and their velocities are
+ * v(t_k).  One launch per step on the context's stream, no synchronisation, nothing crosses to the host; in a timed step
+ * (SPH_OPT_TIMING) it falls into neighbour_ms.  With no set registered (never set, or cleared) both step calls enqueue exactly what
+ * they enqueue without this section.  The per-kernel entry points (sph_compute_densities, ...) and the slab calls never advance it.
+ * GATHER of one tracer at position p (f32): its cell coordinates are c_a = (int)(p_a / grid_size) -- the IEEE f32 division and the
+ * truncation the sort hashes the particles with, here WITHOUT a clamp.  CANDIDATES are the records of the 27 cells (c0+i, c1+j, c2+k),
+ * i, j, k in {-1, 0, 1}; a cell with a coordinate outside [0, grid_num) is skipped; cell f (flat index (cx * ny + cy) * nz + cz)
+ * holds the records [f > 0 ? cell_end[f-1] : 0, cell_end[f]).  (The sort clamps a PARTICLE's cell coordinates into the grid, so a
+ * particle outside the domain is a candidate through the border cell it was hashed into.)  A candidate CONTRIBUTES iff it is
+ * SELECTED by the set's SphSampleSelect (as in "Field sampling") and the PAIR TERM of that section admits it: the same dx, r2, r, q,
+ * W, w sequence, verbatim, with inv_h = 1.f / support_radius formed in f32 by the library, the correctly rounded sqrt and the clamp
+ * of w to [0, 4].  So the contributing set is "in the 27 cells AND q <= 1.0f": a record that a rounding error puts outside that block
+ * does not contribute even if its q <= 1.0f.  Per tracer, over its contributing candidates:
+ *     count  += 1                                                                        (i32)
+ *     weight += llrint((double)w * 2^30)                                                 (i64)
+ *     sum_a  += llrint(((double)w * (double)fmaxf(fminf(v_a, 2^24), -2^24)) * 2^30)      (i64; a = x, y, z)
+ * the sampler's scale, rounding and bounds.  All sums are integers: the result does not depend on the order of the records or on how
+ * the work is split.
+ * ADVANCE: min_weight = max(llrint((double)min_fill * 2^30), 1), computed once per set.  A tracer is WET this step iff
+ * weight >= min_weight.  A wet tracer moves, in f32 with the multiply and the add NOT contracted:
+ *     u_a = (float)((double)sum_a / (double)weight);   xn_a = x_a + dt * u_a;   x_a = fminf(fmaxf(xn_a, padding), wall_hi_a)
+ * and its wet_steps += 1.  A dry tracer gets u = 0, keeps its position, and its dry_steps += 1.  dt is the context's f32 dt at that
+ * step (sph_set_dt between calls is honoured).  weight, count and u are those of the LAST advance.
+ * HISTORY: with record_every > 0, every record_every-th advance since the set was made also stores all m new positions as frame f
+ * of a device buffer [record_capacity][m][3] f32 while f < record_capacity; later frames are counted as dropped and not stored.
+ * sph_step(ctx, 1000, ...) then yields whole pathlines in one download at its end.
+ * WHAT IS WRITTEN: the tracer buffers, nothing else.  Density / pressure of a fused step are not materialised, no derived-state flag
+ * is touched (SPH_OPT_SORT_FAST stays eligible): a run with tracers ends bit-identical to the run without.
+ * sph_tracers_set copies the m points (xyz: host pointer, free again when the call returns: the call synchronises), REPLACES the set
+ * and zeroes its counters and its history; m == 0 clears the set and frees nothing.  sph_tracers_info returns m, the advances made,
+ * the frames stored and the frames dropped; it holds no device data and does not synchronise.  sph_tracers_download copies the
+ * state of the m tracers (any pointer may be NULL) and synchronises; sph_tracers_history_download copies the stored frames
+ * [frames][m][3], `frames` being exactly the number stored, and synchronises.  Buffers are allocated by the first set, grow only and
+ * are freed with the context; a context that never sets tracers allocates nothing.
+ * SPH_E_INVALID: m outside [0, SPH_TRACERS_MAX]; a point that is not finite or lies outside [padding, wall_hi_a] on some axis;
+ * min_fill not finite or outside (0, 4]; a negative record_every or record_capacity; record_capacity * m * 12 bytes above 2^31;
+ * material outside [-1, 255] or n_objects outside [0, SPH_SAMPLE_MAX_OBJECTS]; a download whose m (or frames) does not match.
+ * SPH_E_STATE: a download before any set; a slab rank (set and downloads).  A refused call changes nothing: the last good set goes
+ * on being advanced and stays downloadable.  Tracers are not part of a checkpoint.  csrc/sph_tracers.hip describes the kernel.
+ * ==================================================================================== */
+#define SPH_TRACERS_MAX (1 << 22)
+typedef struct SphTracerParams {
+    float min_fill;                 /* a tracer moves iff its Shepard sum (weight / 2^30) reaches this; finite, in (0, 4] */
+    int32_t record_every;           /* 0: no history; k > 0: every k-th advance stores a frame */
+    int32_t record_capacity;        /* frames the history holds */
+    SphSampleSelect select;         /* whose velocity the tracers follow */
+} SphTracerParams;
+typedef struct SphTracerInfo {
+    int32_t m;                      /* tracers of the registered set (0: none) */
+    int32_t reserved_;
+    int64_t advances;               /* since the set was made */
+    int64_t frames;                 /* history frames stored */
+    int64_t dropped;                /* history frames that found the buffer full */
+} SphTracerInfo;
+int32_t sph_tracers_set(SphContext* ctx, const float* xyz /* host, [m][3] */, int32_t m, const SphTracerParams* params);   /* synchronises */
+int32_t sph_tracers_info(SphContext* ctx, SphTracerInfo* info);
+int32_t sph_tracers_download(SphContext* ctx, float* x /*[m][3]*/, float* u /*[m][3]*/, int64_t* weight, int32_t* count,
+                             int32_t* wet_steps, int32_t* dry_steps, int32_t m);   /* any pointer may be NULL; synchronises */
+int32_t sph_tracers_history_download(SphContext* ctx, float* xyz /*[frames][m][3]*/, int64_t frames, int32_t m);   /* synchronises */
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,4 +132,4 @@ class DFSPHSolver(SPHBase):
             return
         self._push()    # the solver knobs are plain attributes, as in the reference; pick up any change
         ids, n = self._dynamic_ids()
-        self.ps._call("sph_dfsph_step", int(n_steps), ids, n)
+        self.ps._step_call("sph_dfsph_step", n_steps, ids, n, self.dt[None])

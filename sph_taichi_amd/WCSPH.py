@@ -44,4 +44,4 @@ class WCSPHSolver(SPHBase):
             return
         self._push()    # stiffness / exponent / viscosity / surface_tension / g are plain attributes, as in the reference
         ids, n = self._dynamic_ids()
-        self.ps._call("sph_step", int(n_steps), ids, n)
+        self.ps._step_call("sph_step", n_steps, ids, n, self.dt[None])

@@ -158,6 +158,18 @@ class SphMeshSpec(C.Structure):
     _fields_ = [("iso", C.c_float), ("cap", C.c_int32)]
 
 
+class SphTracerParams(C.Structure):
+    """Mirror of `struct SphTracerParams` (include/sph_hip.h)."""
+    _fields_ = [("min_fill", C.c_float), ("record_every", C.c_int32), ("record_capacity", C.c_int32), ("select", SphSampleSelect)]
+
+
+class SphTracerInfo(C.Structure):
+    """Mirror of `struct SphTracerInfo` (include/sph_hip.h)."""
+    _fields_ = [("m", C.c_int32), ("reserved_", C.c_int32), ("advances", C.c_int64), ("frames", C.c_int64), ("dropped", C.c_int64)]
+
+
+TRACERS_MAX = 1 << 22
+
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
 SAMPLE_VX, SAMPLE_VY, SAMPLE_VZ, SAMPLE_DENSITY, SAMPLE_PRESSURE = 1, 2, 4, 8, 16
 SAMPLE_MAX_NODES, SAMPLE_MAX_POINTS, SAMPLE_MAX_OBJECTS, SAMPLE_SCALE_LOG2 = 1 << 24, 1024, 32, 30
@@ -301,6 +313,10 @@ SYMBOLS = [
     ("sph_mesh_extract", C.c_int32, [_ctx, C.POINTER(SphMeshSpec)]),
     ("sph_mesh_counts", C.c_int32, [_ctx, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("sph_mesh_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    ("sph_tracers_set", C.c_int32, [_ctx, C.c_void_p, C.c_int32, C.POINTER(SphTracerParams)]),
+    ("sph_tracers_info", C.c_int32, [_ctx, C.POINTER(SphTracerInfo)]),
+    ("sph_tracers_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    ("sph_tracers_history_download", C.c_int32, [_ctx, C.c_void_p, C.c_int64, C.c_int32]),
 ]
 
 _LIB = None

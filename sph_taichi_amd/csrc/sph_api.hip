@@ -430,6 +430,7 @@ int32_t sph_destroy(SphContext* c) {
     sph_surface_release(c);
     sph_sample_release(c);
     sph_mesh_release(c);
+    sph_tracers_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
@@ -942,6 +943,10 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         rc = rc ? rc : sort_no_fold(c, nullptr, true);   // ps.initialize_particle_system()   sph_base.py:264
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
+        if (c->tracers) {   // a registered tracer set advances with v(t_k) through the cell array of this sort (sph_hip.h, "Passive tracers")
+            rc = sph_tracers_advance(c);
+            if (rc) return rc;
+        }
         rc = body(c, ev, dynamic_ids, n_dynamic, it + 1 == n_steps);
         if (rc) return rc;
         if (c->n_kin > 0) {   // registered bodies -> pose(t_end)

@@ -89,6 +89,7 @@ struct SphExport;   // particle export (sph_export.hip): the id table, tile coun
 struct SphSurface;  // surface frames (sph_surface.hip): the style and the per-pixel planes; null until sph_surface_set_params
 struct SphSample;   // field sampling (sph_sample.hip): the grid's and the points' planes; null until sph_sample_grid / sph_sample_points
 struct SphMesh;     // mesh extraction (sph_mesh.hip): the classification, the cell -> vertex map and the mesh's buffers; null until sph_mesh_extract
+struct SphTracers;  // passive tracers (sph_tracers.hip): the set's buffers, parameters and counters; null until sph_tracers_set
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -210,6 +211,7 @@ struct SphContext {
     SphSurface* surface;
     SphSample* sample;
     SphMesh* mesh;
+    SphTracers* tracers;
     // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
     double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
@@ -310,6 +312,8 @@ void sph_export_release(SphContext* c);  // sph_export.hip: frees the export's i
 void sph_surface_release(SphContext* c); // sph_surface.hip: frees the surface frame's planes (sph_destroy)
 void sph_sample_release(SphContext* c);  // sph_sample.hip: frees the sampled planes (sph_destroy)
 void sph_mesh_release(SphContext* c);    // sph_mesh.hip: frees the extraction's scratch and the mesh's buffers (sph_destroy)
+void sph_tracers_release(SphContext* c); // sph_tracers.hip: frees the tracer buffers and the history (sph_destroy)
+int sph_tracers_advance(SphContext* c);   // sph_tracers.hip: the step loops' hook behind the sort: one launch, or nothing when no set is registered
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -5,8 +5,8 @@
 // pressure is asked for (+ 16 B); writes its own planes.  Never reads the cell array, touches nothing of the sort or the sweeps and
 // writes no particle state.
 //
-// Pair term of sample position p and selected particle j (f32, in this order, nothing contracted; sample_pair() below, shared by the
-// grid and the points kernels so that the two cannot disagree):
+// Pair term of sample position p and selected particle j (f32, in this order, nothing contracted; sample_pair() of sph_sample_pair.h,
+// shared by the grid and the points kernels and by the tracer gather so that they cannot disagree):
 //     dx = p.x - x_j.x (dy, dz alike);  r2 = (dx*dx + dy*dy) + dz*dz;  r = correctly rounded sqrtf(r2);  q = r * inv_h
 //     the pair contributes  <=>  q <= 1.0f                                  (a NaN does not contribute)
 //     W = q <= 0.5f ? k_w * ((6.f*q3 - 6.f*q2) + 1.f)  with q2 = q*q, q3 = q2*q  :  (k_w * 2.f) * ((t*t)*t)  with t = 1.f - q
@@ -41,6 +41,7 @@
 #include <cmath>
 #include "sph_observe.h"
 #include "sph_sample_grid.h"
+#include "sph_sample_pair.h"
 
 #pragma clang fp contract(off)
 
@@ -51,7 +52,6 @@
 #define SP_CHUNK 512              // points per LDS chunk: 512 * (12 + 7 * 8) B = 34,816 B
 #define SP_LDS_BYTES (SP_CHUNK * (12 + SG_MAX_CHANNELS * 8))   // the budget the gradient instance sizes its chunk from
 #define SP_MAX_BLOCKS 1024
-#define S_FIELD_LIMIT 16777216.f  // 2^24
 #define S_ALL_FIELDS (SPH_SAMPLE_VX | SPH_SAMPLE_VY | SPH_SAMPLE_VZ | SPH_SAMPLE_DENSITY | SPH_SAMPLE_PRESSURE)
 
 struct SphSample {
@@ -71,8 +71,6 @@ struct SphSample {
     float pts_host[3 * SPH_SAMPLE_MAX_POINTS];
 };
 
-struct SampleSelect { int material, n_objects; int object_ids[SPH_SAMPLE_MAX_OBJECTS]; };
-
 struct SampleCommon {
     float inv_h, k_w;
     int fields;               // mask
@@ -89,44 +87,6 @@ struct SampleGridDev {
 };
 
 struct NodeBox { int lo[3], hi[3]; };   // inclusive; empty when lo > hi on any axis
-
-__device__ __forceinline__ bool sample_selected(int fl, const SampleSelect& s) {
-    if (s.material >= 0 && sph_flags_material(fl) != s.material) return false;
-    if (s.n_objects > 0) {
-        const int obj = sph_flags_object(fl);
-        bool in = false;
-        for (int k = 0; k < s.n_objects; ++k) in = in || obj == s.object_ids[k];   // uniform index: scalar loads
-        return in;
-    }
-    return true;
-}
-
-struct SamplePairGeom { float d[3], r, q; };   // what the gradient term reuses of the pair term
-
-// THE pair term: does particle X = (x, y, z, m_V) contribute to position p, and with which weight
-__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w, SamplePairGeom& geom) {
-    const float dx = px - X.x, dy = py - X.y, dz = pz - X.z;
-    const float r2 = (dx * dx + dy * dy) + dz * dz;
-    const float r = sqrtf(r2);   // the correctly rounded one (hipcc's default for sqrtf; __fsqrt_rn is the 1-ulp v_sqrt_f32 here)
-    const float q = r * inv_h;
-    if (!(q <= 1.0f)) return false;
-    geom.d[0] = dx; geom.d[1] = dy; geom.d[2] = dz; geom.r = r; geom.q = q;
-    float W;
-    if (q <= 0.5f) {
-        const float q2 = q * q, q3 = q2 * q;
-        W = k_w * ((6.f * q3 - 6.f * q2) + 1.f);
-    } else {
-        const float t = 1.f - q;
-        W = (k_w * 2.f) * ((t * t) * t);
-    }
-    w = fminf(fmaxf(X.w * W, 0.f), 4.f);
-    return true;
-}
-
-__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w) {
-    SamplePairGeom unused;
-    return sample_pair(px, py, pz, X, inv_h, k_w, w, unused);
-}
 
 // THE gradient term of a contributing pair: g_b = u * e_b, dimensionless (h grad w); zero on every axis when r == 0
 __device__ __forceinline__ void sample_gradient(const SamplePairGeom& p, float m_V, float k_w, float g[3]) {
@@ -145,10 +105,6 @@ __device__ __forceinline__ void sample_gradient(const SamplePairGeom& p, float m
         g[b] = u * e;
     }
 }
-
-__device__ __forceinline__ float sample_clamp_field(float a) { return fmaxf(fminf(a, S_FIELD_LIMIT), -S_FIELD_LIMIT); }
-__device__ __forceinline__ long long sample_term(float w, float a) { return llrint(((double)w * (double)a) * (double)(1 << SPH_SAMPLE_SCALE_LOG2)); }
-__device__ __forceinline__ long long sample_weight_term(float w) { return llrint((double)w * (double)(1 << SPH_SAMPLE_SCALE_LOG2)); }
 
 __device__ __forceinline__ float bcast(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 __device__ __forceinline__ int bcast(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }

@@ -1,0 +1,57 @@
+// sph_sample_pair.h -- THE pair term of the field sampling (include/sph_hip.h, "Field sampling") and its fixed-point terms, shared by
+// the scatter sampler (sph_sample.hip) and the tracer gather (sph_tracers.hip) so that the two cannot disagree: who is selected, does
+// particle j contribute to position p and with which weight, and what one contributing pair adds to the i64 sums.  Device code only;
+// everything here is compiled with contraction off (the pragma below holds for the rest of the including file as well: both users
+// want that).
+#pragma once
+#include "sph_internal.h"
+
+#pragma clang fp contract(off)
+
+#define S_FIELD_LIMIT 16777216.f  // 2^24
+
+struct SampleSelect { int material, n_objects; int object_ids[SPH_SAMPLE_MAX_OBJECTS]; };
+
+#ifdef __HIPCC__
+__device__ __forceinline__ bool sample_selected(int fl, const SampleSelect& s) {
+    if (s.material >= 0 && sph_flags_material(fl) != s.material) return false;
+    if (s.n_objects > 0) {
+        const int obj = sph_flags_object(fl);
+        bool in = false;
+        for (int k = 0; k < s.n_objects; ++k) in = in || obj == s.object_ids[k];   // uniform index: scalar loads
+        return in;
+    }
+    return true;
+}
+
+struct SamplePairGeom { float d[3], r, q; };   // what the gradient term reuses of the pair term
+
+// THE pair term: does particle X = (x, y, z, m_V) contribute to position p, and with which weight
+__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w, SamplePairGeom& geom) {
+    const float dx = px - X.x, dy = py - X.y, dz = pz - X.z;
+    const float r2 = (dx * dx + dy * dy) + dz * dz;
+    const float r = sqrtf(r2);   // the correctly rounded one (hipcc's default for sqrtf; __fsqrt_rn is the 1-ulp v_sqrt_f32 here)
+    const float q = r * inv_h;
+    if (!(q <= 1.0f)) return false;
+    geom.d[0] = dx; geom.d[1] = dy; geom.d[2] = dz; geom.r = r; geom.q = q;
+    float W;
+    if (q <= 0.5f) {
+        const float q2 = q * q, q3 = q2 * q;
+        W = k_w * ((6.f * q3 - 6.f * q2) + 1.f);
+    } else {
+        const float t = 1.f - q;
+        W = (k_w * 2.f) * ((t * t) * t);
+    }
+    w = fminf(fmaxf(X.w * W, 0.f), 4.f);
+    return true;
+}
+
+__device__ __forceinline__ bool sample_pair(float px, float py, float pz, const float4& X, float inv_h, float k_w, float& w) {
+    SamplePairGeom unused;
+    return sample_pair(px, py, pz, X, inv_h, k_w, w, unused);
+}
+
+__device__ __forceinline__ float sample_clamp_field(float a) { return fmaxf(fminf(a, S_FIELD_LIMIT), -S_FIELD_LIMIT); }
+__device__ __forceinline__ long long sample_term(float w, float a) { return llrint(((double)w * (double)a) * (double)(1 << SPH_SAMPLE_SCALE_LOG2)); }
+__device__ __forceinline__ long long sample_weight_term(float w) { return llrint((double)w * (double)(1 << SPH_SAMPLE_SCALE_LOG2)); }
+#endif  // __HIPCC__

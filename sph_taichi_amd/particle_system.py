@@ -114,6 +114,7 @@ class ParticleSystem:
         self._motions = dict(getattr(sc, "motions", {}))     # object id -> motion.Motion; pushed by SPHBase.initialize()
         if self._motions and slab is not None:
             raise NotImplementedError("kinematic bodies (\"motion\" in the scene file) exist on single-domain contexts only")
+        self.tracers = None      # the registered tracer set (tracers.Tracers): None until set_tracers
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -468,6 +469,34 @@ class ParticleSystem:
         (synchronises).  Reads the records; changes nothing a later step reads."""
         from . import mesh as _mesh
         return _mesh.surface_mesh(self, spacing=spacing, origin=origin, shape=shape, iso=iso, cap=cap, material=material, objects=objects)
+
+    def set_tracers(self, points, min_fill=0.2, record_every=0, record_capacity=0, material="fluid", objects=None):
+        """Register passive tracers at `points` [[x, y, z], ...] (up to 2^22, inside [padding, domain_size - padding]): from now on
+        every step of the device loop (`solver.step(n)`) moves each of them with the Shepard mean of the velocity of the selected
+        particles (`material`, `objects` as for `sample_grid`) in the 27 cells around it, on the device.  A tracer whose Shepard
+        sum is below `min_fill` stays where it is for that step (0.2 is a quarter of the 0.8 inside fluid at rest spacing: below
+        it the mean rests on one or two particles).  `record_every=k` with `record_capacity=n` keeps the positions after every
+        k-th advance, up to n frames, on the device (`tracers.paths()`).  Replaces the set; returns `self.tracers`
+        (tracers.Tracers).  Tracers are not part of `save_state`."""
+        from . import tracers as _tracers
+        self.tracers = _tracers.set_tracers(self, points, min_fill=min_fill, record_every=record_every,
+                                            record_capacity=record_capacity, material=material, objects=objects)
+        return self.tracers
+
+    def clear_tracers(self):
+        """Remove the tracer set: the steps enqueue what they did before any was set.  `self.tracers` becomes an empty set."""
+        from . import tracers as _tracers
+        self.tracers = _tracers.clear_tracers(self)
+
+    def _step_call(self, name, n_steps, ids, n_ids, dt):
+        """sph_step / sph_dfsph_step; with tracers registered, the times of the history frames the call stored are noted."""
+        tr = self.tracers if self.tracers is not None and self.tracers.m > 0 else None
+        t0 = self.time if tr is not None else 0.0
+        try:
+            self._call(name, int(n_steps), ids, n_ids)
+        finally:
+            if tr is not None:
+                tr._after_steps(t0, dt)
 
     def build_time_step_controller(self, solver):
         """A `timestep.TimeStepController` if the scene's Configuration has an "adaptiveTimeStep" object, else None."""

@@ -42,6 +42,10 @@ Without the keys nothing changes.
 A Configuration with "exportMesh": {"spacing": s, "origin": [..], "shape": [..], "iso": 0.4, "cap": true, "objects": [0]} (every key
 optional) writes `{scene}_output/surface_{cnt:06}.ply` per exported interval: the fluid surface as an indexed triangle mesh with
 normals, extracted on the device from such a grid (mesh.py), a binary PLY.
+A Configuration with "tracers": {"points": [[x, y, z], ...]} or {"lattice": {"start": [..], "end": [..], "spacing": s}}, plus
+"recordEvery" (default 1), "minFill" (default 0.2) and "objects", registers passive tracers after initialize() (tracers.py): they
+are advected on the device inside every step, and `{scene}_output/tracers_{cnt:06}.vtk` per exported interval holds the pathlines
+so far (legacy ASCII POLYDATA, one polyline per tracer, point data `time`); `--tracers out.vtk` writes the final pathlines.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -84,6 +88,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--probes", default="", metavar="PATH",
                     help="write one JSON line per exported interval here: frame, time and the scene's \"probes\" points sampled "
                          "from the fluid (count, fill, the fields)")
+    ap.add_argument("--tracers", default="", metavar="PATH",
+                    help="write the pathlines of the scene's \"tracers\" here after the last frame (legacy ASCII VTK polylines)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
                     help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
@@ -122,7 +128,11 @@ def main(argv=None):
         raise ValueError('--probes needs a "probes" object in the scene\'s Configuration')
     from . import mesh as _mesh
     mesh_spec = _mesh.mesh_config(config)              # "exportMesh": None when the key is absent
-    if output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None:
+    from . import tracers as _tracers
+    tracers_spec = _tracers.tracers_config(config)     # "tracers": None when the key is absent
+    if args.tracers and tracers_spec is None:
+        raise ValueError('--tracers needs a "tracers" object in the scene\'s Configuration')
+    if output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None:
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -149,6 +159,11 @@ def main(argv=None):
         print(f"restored {args.load_state} (frames done: {int(meta.get('frames', 0))})")
     if args.timing:
         ps.set_option(_lib.OPT_TIMING, 1)
+    if tracers_spec is not None:
+        m = tracers_spec["points"].shape[0]
+        ps.set_tracers(tracers_spec["points"], min_fill=tracers_spec["min_fill"], record_every=tracers_spec["record_every"],
+                       record_capacity=_tracers.history_capacity(m, args.frames * substeps, tracers_spec["record_every"]),
+                       objects=tracers_spec["objects"])
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
     probes_out = open(args.probes, "w") if probes_spec is not None else None
@@ -161,7 +176,7 @@ def main(argv=None):
         if args.heightmap_dir:
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
-    cnt = cnt_ply = frames_written = particle_files = grid_files = mesh_files = 0
+    cnt = cnt_ply = frames_written = particle_files = grid_files = mesh_files = tracer_files = 0
     render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
@@ -189,6 +204,9 @@ def main(argv=None):
         if mesh_spec is not None and cnt % output_interval == 0:
             ps.surface_mesh(**mesh_spec).write_ply(f"{scene_name}_output/surface_{cnt:06}.ply", comments=(f"frame {cnt}",))
             mesh_files += 1
+        if tracers_spec is not None and cnt % output_interval == 0:
+            ps.tracers.write_vtk(f"{scene_name}_output/tracers_{cnt:06}.vtk")
+            tracer_files += 1
         if probes_out is not None and cnt % output_interval == 0:
             probes = ps.sample_points(**probes_spec)
             probes_out.write(json.dumps({"frame": cnt, "time": probes.time, "probes": probes.rows()}) + "\n")
@@ -249,6 +267,12 @@ def main(argv=None):
         report["grid_files_written"] = grid_files
     if mesh_files:
         report["mesh_files_written"] = mesh_files
+    if tracers_spec is not None:
+        info = ps.tracers.info()
+        report["tracer_files_written"] = tracer_files
+        report["tracers"] = {"m": info.m, "advances": info.advances, "frames": info.frames, "dropped": info.dropped}
+        if args.tracers:
+            ps.tracers.write_vtk(args.tracers)
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
