@@ -15,6 +15,8 @@ import math
 
 import numpy as np
 
+from . import selection
+
 V_SCALE_LOG2 = 20                    # the velocity sums are fixed point: llrint(v * 2^20) per particle and component
 COLUMNS_MAX = 1 << 20
 
@@ -154,15 +156,10 @@ def gauge_rows(cmap: ColumnMap, points):
 def gauges_config(config) -> dict:
     """The scene's "gauges" object: {"axis": 1, "cell": c, "points": [[a, b], ...]}.  Key absent: axis 1, the default cell
     (None: the support radius) and no points.  A misspelt key raises."""
-    spec = config.get_cfg("gauges")
     out = {"axis": 1, "cell": None, "points": []}
+    spec = selection.config_object(config, "gauges", out)
     if spec is None:
         return out
-    if not isinstance(spec, dict):
-        raise ValueError('"gauges" must be an object')
-    unknown = set(spec) - set(out)
-    if unknown:
-        raise ValueError(f'"gauges": unknown key(s) {sorted(unknown)}')
     out["axis"] = int(spec.get("axis", 1))
     horizontal_axes(out["axis"])
     if spec.get("cell") is not None:

@@ -62,13 +62,15 @@ __global__ __launch_bounds__(ETPB) void k_export_clear(int* __restrict__ slot, i
     if (p < 4) counters[p] = 0u;
 }
 
+struct ExportMark { int pid_stride, pid_phase, use_box; float box_lo[3], box_hi[3]; };   // what k_export_mark reads of the checked SphExportParams beside the SphSel
+
 // grid = ceil(tiles / tiles_per_block) blocks of four waves; block b takes the tiles (256 records each) [b, b + 1) * tiles_per_block
 __global__ __launch_bounds__(ETPB) void k_export_mark(const float4* __restrict__ xm, const float4* __restrict__ vf, const float4* __restrict__ aux,
-                                                      int N, int cold_cap, int tiles_per_block, SphExportParams p, int* __restrict__ slot,
+                                                      int N, int cold_cap, int tiles_per_block, ExportMark p, SphSel sel, int* __restrict__ slot,
                                                       unsigned* __restrict__ counters) {
     __shared__ int wave_selected[EWAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool need_flags = p.material >= 0 || p.n_objects > 0;
+    const bool need_flags = sph_sel_any(sel);
     int n_selected = 0;   // wave-uniform
     const long long first = (long long)blockIdx.x * tiles_per_block * ETPB;
     // wave-uniform bounds: all 64 lanes make every trip (the ballot needs them)
@@ -80,16 +82,7 @@ __global__ __launch_bounds__(ETPB) void k_export_mark(const float4* __restrict__
         if (i < N) {
             const int pid = __float_as_int(aux[i].w);
             selected = p.pid_stride == 1 || pid % p.pid_stride == p.pid_phase;
-            if (selected && need_flags) {
-                const int fl = __float_as_int(vf[i].w);
-                if (p.material >= 0) selected = sph_flags_material(fl) == p.material;
-                if (selected && p.n_objects > 0) {
-                    const int obj = sph_flags_object(fl);
-                    bool in = false;
-                    for (int k = 0; k < p.n_objects; ++k) in = in || obj == p.object_ids[k];   // uniform index: scalar loads
-                    selected = in;
-                }
-            }
+            if (selected && need_flags) selected = sph_selected(__float_as_int(vf[i].w), sel);
             if (selected && p.use_box) {
                 const float4 X = xm[i];
                 selected = X.x >= p.box_lo[0] && X.x <= p.box_hi[0] && X.y >= p.box_lo[1] && X.y <= p.box_hi[1] &&
@@ -264,7 +257,8 @@ int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
     if (int rc = sph_observe_enter(c, "sph_export_select", " (its ghost records would be exported twice); particles are exported from single-domain contexts only")) return rc;
     if (!(p->fields & SPH_EXPORT_X)) return sph_fail(c, SPH_E_INVALID, "sph_export_select: fields must hold SPH_EXPORT_X (the position is always exported)");
     if (p->fields & ~E_ALL_FIELDS) return sph_fail(c, SPH_E_INVALID, "sph_export_select: fields holds unknown bits");
-    if (p->n_objects < 0 || p->n_objects > SPH_EXPORT_MAX_OBJECTS) {
+    SphSel sel;   // (the material's range is not checked here: an id no particle has selects nothing)
+    if (sph_sel_make(p->material, p->n_objects, p->object_ids, false, &sel) == SPH_SEL_BAD_COUNT) {
         snprintf(c->err, sizeof(c->err), "sph_export_select: n_objects = %d, must be in [0, SPH_EXPORT_MAX_OBJECTS = %d]", p->n_objects, SPH_EXPORT_MAX_OBJECTS);
         return SPH_E_INVALID;
     }
@@ -286,7 +280,8 @@ int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
     SPH_LAUNCH_CHECK(c);
     if (N > 0) {
         const SphWalk w = sph_observe_walk(N, ETPB, E_MARK_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_export_mark, dim3(w.blocks), dim3(ETPB), 0, c->stream, in.xm, in.vf, in.aux, N, c->cold_cap, w.per_block, *p, s->table, s->counters);
+        const ExportMark m{p->pid_stride, p->pid_phase, p->use_box, {p->box_lo[0], p->box_lo[1], p->box_lo[2]}, {p->box_hi[0], p->box_hi[1], p->box_hi[2]}};
+        hipLaunchKernelGGL(k_export_mark, dim3(w.blocks), dim3(ETPB), 0, c->stream, in.xm, in.vf, in.aux, N, c->cold_cap, w.per_block, m, sel, s->table, s->counters);
         SPH_LAUNCH_CHECK(c);
     }
     hipLaunchKernelGGL(k_export_count, dim3(s->n_tiles), dim3(ETPB), 0, c->stream, s->table, s->tile_count);

@@ -1,7 +1,9 @@
 // sph_observe.h -- what the read-only observers of the particle state share (sph_diag.hip, sph_columns.hip, sph_export.hip,
-// sph_render.hip, sph_surface.hip): the view of the live records, the entry checks, the allocation and download sequences, the
-// grid of a contiguous walk and the 64-bit shuffles.  An observer reads the records behind whatever the stream holds, writes
-// buffers of its own and no particle state.
+// sph_render.hip, sph_surface.hip, sph_sample.hip, sph_mesh.hip, sph_tracers.hip): the view of the live records, the entry
+// checks, the allocation and download sequences, the grid of a contiguous walk, the 64-bit shuffles and THE particle selection
+// (SphSel: who is selected by a material and a list of object ids -- the export, the field colouring of both frame styles, the
+// field range, the samplers with the mesh cut from their grid, and the tracers all ask sph_selected).  An observer reads the
+// records behind whatever the stream holds, writes buffers of its own and no particle state.
 #pragma once
 #include <new>
 
@@ -75,7 +77,38 @@ static inline SphWalk sph_observe_walk(int N, int threads, int max_blocks) {
     return SphWalk{(tiles + per_block - 1) / per_block, per_block};
 }
 
+// The selection of SphExportParams, SphFieldColour and SphSampleSelect (include/sph_hip.h): material -1 = any, n_objects 0 = all.
+// By value into the launches, so that the ids are kernel arguments.
+struct SphSel { int material, n_objects; int object_ids[32]; };
+static_assert(SPH_EXPORT_MAX_OBJECTS == 32 && SPH_FIELD_MAX_OBJECTS == 32 && SPH_SAMPLE_MAX_OBJECTS == 32,
+              "the three public object-list limits are one limit: SphSel holds 32 ids");
+
+static constexpr bool sph_sel_any(const SphSel& s) { return s.material >= 0 || s.n_objects > 0; }   // host and device; false: nobody's flags need reading
+
+// A public selection into *out, checked: n_objects in [0, 32] and, with check_material, material in [-1, 255].  The first
+// n_objects ids are copied, the rest are 0.  The caller words its own message from the code.
+enum { SPH_SEL_OK, SPH_SEL_BAD_MATERIAL, SPH_SEL_BAD_COUNT };
+static inline int sph_sel_make(int material, int n_objects, const int32_t* ids, bool check_material, SphSel* out) {
+    if (check_material && (material < -1 || material > 255)) return SPH_SEL_BAD_MATERIAL;
+    if (n_objects < 0 || n_objects > 32) return SPH_SEL_BAD_COUNT;
+    out->material = material;
+    out->n_objects = n_objects;
+    for (int k = 0; k < 32; ++k) out->object_ids[k] = k < n_objects ? ids[k] : 0;
+    return SPH_SEL_OK;
+}
+
 #ifdef __HIPCC__
+__device__ __forceinline__ bool sph_selected(int flags, const SphSel& s) {
+    if (s.material >= 0 && sph_flags_material(flags) != s.material) return false;
+    if (s.n_objects > 0) {
+        const int obj = sph_flags_object(flags);
+        bool in = false;
+        for (int k = 0; k < s.n_objects; ++k) in = in || obj == s.object_ids[k];   // uniform index: scalar loads
+        return in;
+    }
+    return true;
+}
+
 __device__ __forceinline__ long long shfl_xor_i64(long long v, int m) {
     const int lo = __shfl_xor((int)(v & 0xffffffffll), m, 64), hi = __shfl_xor((int)(v >> 32), m, 64);
     return ((long long)hi << 32) | (unsigned)lo;

@@ -110,7 +110,7 @@ template <int LAYER>
 __device__ __forceinline__ int frame_colour(const FrameField& ff, const float4& x, const float4* __restrict__ aux,
                                             const int* __restrict__ color_cold, int cold_cap, int p, float kc[3]) {
     const float4 V = ff.vf[p], A = aux[p];
-    const bool sel = field_selected(ff.sel, __float_as_int(V.w));
+    const bool sel = sph_selected(__float_as_int(V.w), ff.sel.who);
     const int idx = sel ? field_index(ff.sel, field_value(ff.sel, x, V, A)) : FIELD_IDX_NONE;
     if (LAYER != LAYER_FLUID_FIELD) {
         if (sel) field_lut_colour(ff.lut, idx, kc);
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(RTPB) void k_field_range(const float4* __restrict__
         if (i >= N) break;
         const float4 V = vf[i];
         const int flags = __float_as_int(V.w);
-        if (!field_selected(sel, flags)) continue;
+        if (!sph_selected(flags, sel.who)) continue;
         const int oid = sph_flags_object(flags);
         bool visible = true;
         for (int k = 0; k < hidden.n; ++k) visible = visible && hidden.ids[k] != oid;
@@ -281,12 +281,12 @@ __global__ __launch_bounds__(RTPB) void k_field_range(const float4* __restrict__
 // the selection part of a SphFieldColour into sel; a message = what is wrong with it
 static const char* make_selection(const SphFieldColour& fc, FieldSel& sel) {
     if (fc.field < 0 || fc.field >= SPH_FIELD_COUNT_) return "unknown field (enum SphColourField)";
-    if (fc.material < -1 || fc.material > 255) return "material must be -1 or in [0, 255]";
-    if (fc.n_objects < 0 || fc.n_objects > SPH_FIELD_MAX_OBJECTS) return "n_objects must be in [0, SPH_FIELD_MAX_OBJECTS = 32]";
+    switch (sph_sel_make(fc.material, fc.n_objects, fc.object_ids, true, &sel.who)) {
+        case SPH_SEL_BAD_MATERIAL: return "material must be -1 or in [0, 255]";
+        case SPH_SEL_BAD_COUNT: return "n_objects must be in [0, SPH_FIELD_MAX_OBJECTS = 32]";
+    }
     if (!isfinite(fc.axis_origin)) return "axis_origin must be finite";
-    memset(&sel, 0, sizeof(sel));
-    sel.field = fc.field; sel.material = fc.material; sel.n_objects = fc.n_objects;
-    for (int k = 0; k < fc.n_objects; ++k) sel.object_ids[k] = fc.object_ids[k];
+    sel.field = fc.field;
     sel.origin = fc.axis_origin;
     sel.lo = 0.0f; sel.inv = 1.0f;
     return nullptr;

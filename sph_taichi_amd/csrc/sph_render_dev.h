@@ -31,9 +31,9 @@ struct RenderCam {
 // Field colouring (include/sph_hip.h, "Field colouring of the frames"; sph_render.hip states the arithmetic): which particles
 // take a table colour, from which field, and the range as lo and inv = 1 / (hi - lo).  By value into the launches, like RenderCam.
 struct FieldSel {
-    int field, material, n_objects;
-    int object_ids[SPH_FIELD_MAX_OBJECTS];
+    int field;
     float lo, inv, origin;
+    SphSel who;
 };
 #define FIELD_IDX_NONE 256                 // "this fluid fragment's particle is not selected" in the low half of a field-index key
 
@@ -176,18 +176,7 @@ __device__ __forceinline__ void surface_field_fragment(const RenderCam& cam, con
     if (zb < (unsigned)(keys[p] >> 32)) atomicAdd(thick + p, (unsigned)((hh / cam.radius) * 256.0f + 0.5f));   // (the opaque layer is final)
 }
 
-// ---- field colouring: selection, field value, table index (the block "Field colouring" of sph_render.hip) ----
-__device__ __forceinline__ bool field_selected(const FieldSel& f, int flags) {
-    if (f.material >= 0 && sph_flags_material(flags) != f.material) return false;
-    if (f.n_objects > 0) {
-        const int oid = sph_flags_object(flags);
-        bool in = false;
-        for (int k = 0; k < f.n_objects; ++k) in = in || oid == f.object_ids[k];    // uniform index: scalar loads
-        return in;
-    }
-    return true;
-}
-
+// ---- field colouring: field value, table index (the block "Field colouring" of sph_render.hip; the selection: sph_observe.h) ----
 __device__ __forceinline__ float field_value(const FieldSel& f, const float4& X, const float4& V, const float4& A) {
     switch (f.field) {
         case SPH_FIELD_SPEED: return sqrtf((V.x * V.x + V.y * V.y) + V.z * V.z);

@@ -75,7 +75,7 @@ struct SampleCommon {
     float inv_h, k_w;
     int fields;               // mask
     int channels;             // 2 + popcount(fields)
-    SampleSelect sel;
+    SphSel sel;
 };
 
 struct SampleGridDev {
@@ -157,7 +157,7 @@ __device__ __forceinline__ void sample_grid_body(const float4* __restrict__ xm, 
         if (i < last) {
             X = xm[i];
             const float4 V = vf[i];
-            if (sample_selected(__float_as_int(V.w), q.sel)) {
+            if (sph_selected(__float_as_int(V.w), q.sel)) {
                 b = sample_footprint(g, X);
                 act = !box_empty(b);
                 if (act) {
@@ -245,7 +245,7 @@ __device__ __forceinline__ void sample_points_body(unsigned char* sample_lds, co
         __syncthreads();
         for (long long i = first + threadIdx.x; i < last; i += STPB) {
             const float4 V = vf[i];
-            if (!sample_selected(__float_as_int(V.w), q.sel)) continue;
+            if (!sph_selected(__float_as_int(V.w), q.sel)) continue;
             const float4 X = xm[i];
             float A[5] = {sample_clamp_field(V.x), sample_clamp_field(V.y), sample_clamp_field(V.z), 0.f, 0.f};
             if (need_aux) {
@@ -322,19 +322,12 @@ static int sample_state(SphContext* c, const char* who) {
 static int sample_common(SphContext* c, const char* who, int32_t fields, const SphSampleSelect* sel, float inv_h, SampleCommon* q) {
     if (fields & ~S_ALL_FIELDS) { snprintf(c->err, sizeof(c->err), "%s: fields holds unknown bits", who); return SPH_E_INVALID; }
     if (!sel) { snprintf(c->err, sizeof(c->err), "%s: the selection is NULL", who); return SPH_E_INVALID; }
-    if (sel->material < -1 || sel->material > 255) { snprintf(c->err, sizeof(c->err), "%s: material = %d, must be in [-1, 255]", who, sel->material); return SPH_E_INVALID; }
-    if (sel->n_objects < 0 || sel->n_objects > SPH_SAMPLE_MAX_OBJECTS) {
-        snprintf(c->err, sizeof(c->err), "%s: n_objects = %d, must be in [0, SPH_SAMPLE_MAX_OBJECTS = %d]", who, sel->n_objects, SPH_SAMPLE_MAX_OBJECTS);
-        return SPH_E_INVALID;
-    }
+    if (int rc = sample_select(c, who, *sel, &q->sel)) return rc;
     if (!std::isfinite(inv_h) || !(inv_h > 0.f)) { snprintf(c->err, sizeof(c->err), "%s: inv_h must be finite and positive", who); return SPH_E_INVALID; }
     q->inv_h = inv_h;
     q->k_w = c->p.k_w;
     q->fields = fields;
     q->channels = 2 + __builtin_popcount((unsigned)fields);
-    q->sel.material = sel->material;
-    q->sel.n_objects = sel->n_objects;
-    for (int k = 0; k < SPH_SAMPLE_MAX_OBJECTS; ++k) q->sel.object_ids[k] = k < sel->n_objects ? sel->object_ids[k] : 0;
     return 0;
 }
 

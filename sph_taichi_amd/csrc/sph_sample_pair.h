@@ -1,29 +1,27 @@
 // sph_sample_pair.h -- THE pair term of the field sampling (include/sph_hip.h, "Field sampling") and its fixed-point terms, shared by
-// the scatter sampler (sph_sample.hip) and the tracer gather (sph_tracers.hip) so that the two cannot disagree: who is selected, does
-// particle j contribute to position p and with which weight, and what one contributing pair adds to the i64 sums.  Device code only;
-// everything here is compiled with contraction off (the pragma below holds for the rest of the including file as well: both users
-// want that).
+// the scatter sampler (sph_sample.hip) and the tracer gather (sph_tracers.hip) so that the two cannot disagree: does a selected (sph_observe.h)
+// particle j contribute to position p and with which weight, and what one contributing pair adds to the i64 sums.  Beside them the one
+// host function both users check their public SphSampleSelect with.  Everything here is compiled with contraction off (the pragma
+// below holds for the rest of the including file as well: both users want that).
 #pragma once
-#include "sph_internal.h"
+#include "sph_observe.h"
 
 #pragma clang fp contract(off)
 
 #define S_FIELD_LIMIT 16777216.f  // 2^24
 
-struct SampleSelect { int material, n_objects; int object_ids[SPH_SAMPLE_MAX_OBJECTS]; };
-
-#ifdef __HIPCC__
-__device__ __forceinline__ bool sample_selected(int fl, const SampleSelect& s) {
-    if (s.material >= 0 && sph_flags_material(fl) != s.material) return false;
-    if (s.n_objects > 0) {
-        const int obj = sph_flags_object(fl);
-        bool in = false;
-        for (int k = 0; k < s.n_objects; ++k) in = in || obj == s.object_ids[k];   // uniform index: scalar loads
-        return in;
+// a public SphSampleSelect into *out (the sampler's entries and sph_tracers_set), or SPH_E_INVALID with its message
+static inline int sample_select(SphContext* c, const char* who, const SphSampleSelect& sel, SphSel* out) {
+    switch (sph_sel_make(sel.material, sel.n_objects, sel.object_ids, true, out)) {
+        case SPH_SEL_BAD_MATERIAL: snprintf(c->err, sizeof(c->err), "%s: material = %d, must be in [-1, 255]", who, sel.material); return SPH_E_INVALID;
+        case SPH_SEL_BAD_COUNT:
+            snprintf(c->err, sizeof(c->err), "%s: n_objects = %d, must be in [0, SPH_SAMPLE_MAX_OBJECTS = %d]", who, sel.n_objects, SPH_SAMPLE_MAX_OBJECTS);
+            return SPH_E_INVALID;
     }
-    return true;
+    return 0;
 }
 
+#ifdef __HIPCC__
 struct SamplePairGeom { float d[3], r, q; };   // what the gradient term reuses of the pair term
 
 // THE pair term: does particle X = (x, y, z, m_V) contribute to position p, and with which weight

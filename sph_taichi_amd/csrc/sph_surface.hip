@@ -432,8 +432,8 @@ static int surface_frame(SphContext* c, hipEvent_t* ev) {
     const RenderCam& cam = r->cam;
     if (int rc = surface_alloc(c, s, cam.W, cam.H)) return rc;
     // a field colouring: which of the two layers holds selected particles (a material other than fluid: only the opaque one)
-    const bool opaque_field = r->colour_on && r->sel.material != SPH_MATERIAL_FLUID;
-    const bool fluid_field = r->colour_on && (r->sel.material < 0 || r->sel.material == SPH_MATERIAL_FLUID);
+    const bool opaque_field = r->colour_on && r->sel.who.material != SPH_MATERIAL_FLUID;
+    const bool fluid_field = r->colour_on && (r->sel.who.material < 0 || r->sel.who.material == SPH_MATERIAL_FLUID);
     if (fluid_field)
         if (int rc = surface_field_alloc(c, s, cam.W, cam.H)) return rc;
     if (int rc = frame_colour_prepare(c, r)) return rc;

@@ -36,7 +36,7 @@ struct SphTracers {
     bool have;                // a set has been made (m == 0: it was cleared)
     int record_every, record_capacity;
     long long min_weight;
-    SampleSelect sel;
+    SphSel sel;
     long long advances, frames, dropped;
 };
 
@@ -61,7 +61,7 @@ struct TracerArgs {
     int N, m;
     long long min_weight;
     float* frame;             // null: this advance stores no history frame
-    SampleSelect sel;
+    SphSel sel;
 };
 
 template <int CTRL>
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(TR_TPB) void k_tracers_advance(const float4* __rest
                         last = last > a.N ? a.N : last;
                         for (int k = first + sub; k < last; k += TR_ROW) {
                             const float4 V = vf[k];
-                            if (!sample_selected(__float_as_int(V.w), a.sel)) continue;
+                            if (!sph_selected(__float_as_int(V.w), a.sel)) continue;
                             const float4 X = xm[k];
                             float w;
                             if (!sample_pair(px, py, pz, X, a.inv_h, a.k_w, w)) continue;
@@ -210,12 +210,8 @@ int32_t sph_tracers_set(SphContext* c, const float* xyz, int32_t m, const SphTra
         snprintf(c->err, sizeof(c->err), "%s: a history of %d frames of %d tracers takes %llu bytes, more than 2^31", who, tp->record_capacity, m, hist_bytes);
         return SPH_E_INVALID;
     }
-    const SphSampleSelect& sel = tp->select;
-    if (sel.material < -1 || sel.material > 255) { snprintf(c->err, sizeof(c->err), "%s: material = %d, must be in [-1, 255]", who, sel.material); return SPH_E_INVALID; }
-    if (sel.n_objects < 0 || sel.n_objects > SPH_SAMPLE_MAX_OBJECTS) {
-        snprintf(c->err, sizeof(c->err), "%s: n_objects = %d, must be in [0, SPH_SAMPLE_MAX_OBJECTS = %d]", who, sel.n_objects, SPH_SAMPLE_MAX_OBJECTS);
-        return SPH_E_INVALID;
-    }
+    SphSel sel;
+    if (int rc = sample_select(c, who, tp->select, &sel)) return rc;
     for (int k = 0; k < m; ++k)
         for (int a = 0; a < 3; ++a) {
             const float v = xyz[3 * (size_t)k + a];
@@ -252,8 +248,7 @@ int32_t sph_tracers_set(SphContext* c, const float* xyz, int32_t m, const SphTra
     s->record_every = tp->record_every; s->record_capacity = tp->record_capacity;
     const long long mw = llrint((double)tp->min_fill * (double)(1 << SPH_SAMPLE_SCALE_LOG2));
     s->min_weight = mw < 1 ? 1 : mw;
-    s->sel.material = sel.material; s->sel.n_objects = sel.n_objects;
-    for (int k = 0; k < SPH_SAMPLE_MAX_OBJECTS; ++k) s->sel.object_ids[k] = k < sel.n_objects ? sel.object_ids[k] : 0;
+    s->sel = sel;
     s->advances = s->frames = s->dropped = 0;
     return 0;
 }

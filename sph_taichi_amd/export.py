@@ -10,13 +10,14 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import selection
+from .selection import MATERIALS, MAX_OBJECTS   # noqa: F401  (part of this module's surface)
+
 # optional fields in ROW ORDER: name -> (bit of SphExportParams.fields, columns of the structured array)
 FIELD_BITS = {"velocity": 2, "density": 4, "pressure": 8, "mass": 16, "id": 32, "object": 64}
 FIELD_COLUMNS = {"velocity": (("vx", "<f4"), ("vy", "<f4"), ("vz", "<f4")), "density": (("density", "<f4"),),
                  "pressure": (("pressure", "<f4"),), "mass": (("mass", "<f4"),), "id": (("id", "<i4"),), "object": (("object", "<i4"),)}
 EXPORT_X = 1
-MAX_OBJECTS = 32
-MATERIALS = {"solid": 0, "fluid": 1}
 CONFIG_KEYS = ("objects", "material", "fields", "box", "every", "phase")
 
 
@@ -44,29 +45,8 @@ def select_args(objects=None, material=None, fields=("velocity",), box=None, eve
     mask = EXPORT_X
     for n in names:
         mask |= FIELD_BITS[n]
-    if material is None:
-        mat = -1
-    elif isinstance(material, str):
-        if material not in MATERIALS:
-            raise ValueError(f"material must be one of {list(MATERIALS)} or a material id, not {material!r}")
-        mat = MATERIALS[material]
-    else:
-        mat = _integer(material, "material")
-        if not 0 <= mat <= 255:
-            raise ValueError("a material id is in [0, 255]")
-    if objects is None:
-        ids = []
-    else:
-        if isinstance(objects, (int, np.integer)):
-            objects = [objects]
-        ids = [_integer(o, "an object id") for o in objects]
-        if not ids:
-            raise ValueError("objects is empty: pass None for every object")
-        if len(ids) > MAX_OBJECTS:
-            raise ValueError(f"at most {MAX_OBJECTS} objects can be selected at once")
-        if min(ids) < 0:
-            raise ValueError("an object id is not negative")
-    every, phase = _integer(every, "every"), _integer(phase, "phase")
+    mat, ids = selection.parse(material, objects)
+    every, phase = selection.integer(every, "every"), selection.integer(phase, "phase")
     if every < 1 or every > 2 ** 31 - 1:
         raise ValueError("every must be at least 1")
     if not 0 <= phase < every:
@@ -88,24 +68,13 @@ def select_args(objects=None, material=None, fields=("velocity",), box=None, eve
     return {"fields": names, "mask": mask, "material": mat, "objects": ids, "box": box, "every": every, "phase": phase}
 
 
-def _integer(value, name) -> int:
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, not {value!r}")
-    return int(value)
-
-
 def export_config(config):
     """The scene's "exportParticles" object: {"objects": [0], "material": "fluid", "fields": [...], "box": [[lo], [hi]],
     "every": 1, "phase": 0}, every key optional ({} = every particle, positions only).  Returns the checked keyword arguments
     of `export_particles`, or None when the key is absent.  A misspelt key or a bad value raises ValueError."""
-    spec = config.get_cfg("exportParticles")
+    spec = selection.config_object(config, "exportParticles", CONFIG_KEYS)
     if spec is None:
         return None
-    if not isinstance(spec, dict):
-        raise ValueError('"exportParticles" must be an object')
-    unknown = set(spec) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f'"exportParticles": unknown key(s) {sorted(unknown)}')
     kw = {"objects": spec.get("objects"), "material": spec.get("material"), "fields": tuple(spec.get("fields", ())),
           "box": spec.get("box"), "every": spec.get("every", 1), "phase": spec.get("phase", 0)}
     try:
@@ -169,10 +138,8 @@ def make_params(args: dict):
     import ctypes as C
     from . import _lib
     p = _lib.SphExportParams()
-    p.fields, p.material = args["mask"], args["material"]
-    p.n_objects = len(args["objects"])
-    for k, oid in enumerate(args["objects"]):
-        p.object_ids[k] = oid
+    p.fields = args["mask"]
+    selection.fill(p, args["material"], args["objects"])
     p.pid_stride, p.pid_phase = args["every"], args["phase"]
     p.use_box = 0 if args["box"] is None else 1
     if args["box"] is not None:

@@ -15,6 +15,7 @@ import math
 import numpy as np
 
 from . import sample as _sample
+from . import selection
 
 ISO_MAX = 4.0
 CONFIG_KEYS = ("spacing", "origin", "shape", "iso", "cap", "objects")
@@ -115,19 +116,14 @@ def mesh_config(config):
     """The scene's "exportMesh" object: {"spacing": s, "origin": [..], "shape": [..], "iso": 0.4, "cap": true, "objects": [..]},
     every key optional ({} = the fluid on the default grid).  Returns the keyword arguments of `surface_mesh`, or None when the key
     is absent.  A misspelt key or a bad value raises ValueError."""
-    spec = config.get_cfg("exportMesh")
+    spec = selection.config_object(config, "exportMesh", CONFIG_KEYS)
     if spec is None:
         return None
-    if not isinstance(spec, dict):
-        raise ValueError('"exportMesh" must be an object')
-    unknown = set(spec) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f'"exportMesh": unknown key(s) {sorted(unknown)}')
     kw = {"spacing": spec.get("spacing"), "origin": spec.get("origin"), "shape": spec.get("shape"), "iso": spec.get("iso", 0.4),
           "cap": spec.get("cap", True), "objects": spec.get("objects")}
     try:
         mesh_args(kw["iso"], kw["cap"])
-        _sample.select_args(fields=(), objects=kw["objects"])
+        selection.parse("fluid", kw["objects"])
         if kw["shape"] is not None:
             grid_args(kw["spacing"], kw["origin"], kw["shape"], particle_diameter=1.0, domain_size=(1.0, 1.0, 1.0))
         else:
@@ -157,7 +153,7 @@ def surface_mesh(ps, spacing=None, origin=None, shape=None, iso=0.4, cap=True, m
     import ctypes as C
     from . import _lib
     ma = mesh_args(iso, cap)
-    sel = _sample.select_args(fields=(), material=material, objects=objects)
+    mat, ids = selection.parse(material, objects)
     ga = grid_args(spacing, origin, shape, particle_diameter=ps.particle_diameter, domain_size=ps.domain_size)
     if ps.slab is not None:
         raise NotImplementedError("meshes are extracted on single-domain contexts only: a slab rank's ghost records would be "
@@ -165,7 +161,7 @@ def surface_mesh(ps, spacing=None, origin=None, shape=None, iso=0.4, cap=True, m
     g = _lib.SphSampleGrid()
     g.n = (C.c_int32 * 3)(*ga["shape"])
     g.origin, g.spacing = (C.c_float * 3)(*ga["origin"]), (C.c_float * 3)(*ga["spacing"])
-    g.inv_h, g.fields, g.select = _sample.inv_h_f32(ps.support_radius), 0, _sample.make_select(sel)   # no field planes: the weight alone
+    g.inv_h, g.fields, g.select = _sample.inv_h_f32(ps.support_radius), 0, selection.fill(_lib.SphSampleSelect(), mat, ids)   # no field planes: the weight alone
     ps._call("sph_sample_grid", C.byref(g))
     pos, nrm, tri = extract_raw(ps, ma["iso"], ma["cap"])
     return SurfaceMesh(pos, nrm, tri, time=ps.time, iso=ma["iso"], origin=ga["origin"], spacing=ga["spacing"], shape=ga["shape"])

@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, selection
 
 
 @dataclass
@@ -132,7 +132,6 @@ def surface_params(style: SurfaceStyle) -> "_lib.SphSurfaceParams":
 # ---- field colouring of the frames (csrc/sph_render.hip states the index arithmetic) ----
 # enum SphColourField, in its order
 FIELDS = ("speed", "vx", "vy", "vz", "density", "pressure", "x", "y", "z")
-_MATERIALS = {"fluid": 1, "solid": 0}          # particle_system.py:30-31 of the reference
 # Control points (position in [0, 1], red, green, blue) of the built-in maps; colormap() interpolates between them.
 _COLORMAPS = {
     "heat": ((0.0, 0, 0, 0), (0.3, 160, 0, 0), (0.55, 255, 70, 0), (0.8, 255, 210, 0), (1.0, 255, 255, 255)),
@@ -173,15 +172,7 @@ class FieldColour:
             raise ValueError(f"field must be one of {', '.join(FIELDS)}, not {self.field!r}")
         if self.range is not None:
             self.range = check_range(self.range)
-        if self.material is not None and self.material not in _MATERIALS:
-            raise ValueError(f"material must be \"fluid\", \"solid\" or None, not {self.material!r}")
-        if self.objects is not None:
-            ids = [self.objects] if isinstance(self.objects, (int, np.integer)) else list(self.objects)
-            if any(isinstance(o, bool) or not isinstance(o, (int, np.integer)) or o < 0 for o in ids):
-                raise ValueError("objects must be a list of object ids (integers >= 0) or None")
-            if not ids or len(ids) > _lib.FIELD_MAX_OBJECTS:
-                raise ValueError(f"objects holds {len(ids)} ids: pass None for every object, at most {_lib.FIELD_MAX_OBJECTS} otherwise")
-            self.objects = [int(o) for o in ids]
+        self.objects = selection.parse(self.material, self.objects, material_ids=False)[1] or None   # (names only: no material id)
         self.axis_origin = float(self.axis_origin)
         if not math.isfinite(self.axis_origin):
             raise ValueError("axis_origin must be finite")
@@ -262,11 +253,7 @@ def field_colour_params(colour: FieldColour, rng=(0.0, 1.0)) -> "_lib.SphFieldCo
     """The C struct for `colour` with the range `rng`."""
     p = _lib.SphFieldColour()
     p.field = FIELDS.index(colour.field)
-    p.material = -1 if colour.material is None else _MATERIALS[colour.material]
-    ids = colour.objects or []
-    p.n_objects = len(ids)
-    for k, oid in enumerate(ids):
-        p.object_ids[k] = oid
+    selection.fill(p, -1 if colour.material is None else selection.MATERIALS[colour.material], colour.objects or [])
     p.lo, p.hi = float(rng[0]), float(rng[1])
     p.axis_origin = colour.axis_origin
     return p

@@ -17,21 +17,17 @@ import math
 
 import numpy as np
 
+from . import selection
+from .selection import MATERIALS, MAX_OBJECTS   # noqa: F401  (part of this module's surface)
+
 SCALE_LOG2 = 30                      # the sums are fixed point: llrint(w * 2^30), llrint(w * A * 2^30) per contributing pair
-MAX_NODES, MAX_POINTS, MAX_OBJECTS = 1 << 24, 1024, 32
+MAX_NODES, MAX_POINTS = 1 << 24, 1024
 # user-level field -> the planes it asks for, in the order of the SPH_SAMPLE_* bits
 FIELD_PLANES = {"velocity": ("vx", "vy", "vz"), "density": ("density",), "pressure": ("pressure",)}
 PLANE_BITS = {"vx": 1, "vy": 2, "vz": 4, "density": 8, "pressure": 16}
-MATERIALS = {"solid": 0, "fluid": 1}
 GRID_CONFIG_KEYS = ("spacing", "origin", "shape", "fields", "objects", "gradients")
 PROBES_CONFIG_KEYS = ("points", "fields", "gradients")
 FILL = "fill"                        # the one name `gradients` takes beside those of FIELD_PLANES: the fill gradient alone
-
-
-def _integer(value, name) -> int:
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
-        raise ValueError(f"{name} must be an integer, not {value!r}")
-    return int(value)
 
 
 def _triple(value, name):
@@ -66,28 +62,7 @@ def select_args(fields=("velocity",), material="fluid", objects=None) -> dict:
     mask = 0
     for p in planes:
         mask |= PLANE_BITS[p]
-    if material is None:
-        mat = -1
-    elif isinstance(material, str):
-        if material not in MATERIALS:
-            raise ValueError(f"material must be one of {list(MATERIALS)}, a material id or None (any), not {material!r}")
-        mat = MATERIALS[material]
-    else:
-        mat = _integer(material, "material")
-        if not 0 <= mat <= 255:
-            raise ValueError("a material id is in [0, 255]")
-    if objects is None:
-        ids = []
-    else:
-        if isinstance(objects, (int, np.integer)) and not isinstance(objects, (bool, np.bool_)):
-            objects = [objects]
-        ids = [_integer(o, "an object id") for o in objects]
-        if not ids:
-            raise ValueError("objects is empty: pass None for every object")
-        if len(ids) > MAX_OBJECTS:
-            raise ValueError(f"at most {MAX_OBJECTS} objects can be selected at once")
-        if min(ids) < 0:
-            raise ValueError("an object id is not negative")
+    mat, ids = selection.parse(material, objects)
     return {"fields": names, "planes": planes, "mask": mask, "material": mat, "objects": ids}
 
 
@@ -132,7 +107,7 @@ def grid_args(spacing=None, origin=None, shape=None, *, particle_diameter, domai
             raise ValueError("shape must be three node counts") from e
         if len(shape) != 3:
             raise ValueError("shape must be three node counts")
-        shape = tuple(_integer(n, "a node count") for n in shape)
+        shape = tuple(selection.integer(n, "a node count") for n in shape)
     if min(shape) < 1:
         raise ValueError("every node count must be at least 1 (a slice is a shape with a 1 in it)")
     if shape[0] * shape[1] * shape[2] > MAX_NODES:
@@ -381,14 +356,9 @@ def sample_grid_config(config):
     "gradients": [..]}, every key optional ({} = velocity on the default grid).  Returns the keyword arguments of `sample_grid`
     ("gradients" among them only when the scene names it), or None when the key is absent.  A misspelt key or a bad value
     raises ValueError."""
-    spec = config.get_cfg("sampleGrid")
+    spec = selection.config_object(config, "sampleGrid", GRID_CONFIG_KEYS)
     if spec is None:
         return None
-    if not isinstance(spec, dict):
-        raise ValueError('"sampleGrid" must be an object')
-    unknown = set(spec) - set(GRID_CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f'"sampleGrid": unknown key(s) {sorted(unknown)}')
     kw = {"spacing": spec.get("spacing"), "origin": spec.get("origin"), "shape": spec.get("shape"),
           "fields": _fields_from_spec(spec, "sampleGrid", ("velocity",)), "objects": spec.get("objects")}
     if "gradients" in spec:
@@ -406,14 +376,9 @@ def probes_config(config):
     """The scene's "probes" object: {"points": [[x, y, z], ...], "fields": [..], "gradients": [..]}.  Returns the keyword
     arguments of `sample_points` ("gradients" among them only when the scene names it), or None when the key is absent.  A
     misspelt key or a bad value raises ValueError."""
-    spec = config.get_cfg("probes")
+    spec = selection.config_object(config, "probes", PROBES_CONFIG_KEYS)
     if spec is None:
         return None
-    if not isinstance(spec, dict):
-        raise ValueError('"probes" must be an object')
-    unknown = set(spec) - set(PROBES_CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f'"probes": unknown key(s) {sorted(unknown)}')
     if "points" not in spec:
         raise ValueError('"probes": points is missing')
     try:
@@ -437,11 +402,7 @@ def inv_h_f32(support_radius) -> float:
 def make_select(args: dict):
     """SphSampleSelect of checked arguments (`select_args`)."""
     from . import _lib
-    s = _lib.SphSampleSelect()
-    s.material, s.n_objects = args["material"], len(args["objects"])
-    for k, oid in enumerate(args["objects"]):
-        s.object_ids[k] = oid
-    return s
+    return selection.fill(_lib.SphSampleSelect(), args["material"], args["objects"])
 
 
 def download_grid_raw(ps, grid, n_planes, gradients=None):

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import sample as _sample
+from . import selection
 
 MAX_TRACERS = 1 << 22
 MAX_HISTORY_BYTES = 1 << 31
@@ -71,15 +72,14 @@ def set_args(points, min_fill=0.2, record_every=0, record_capacity=0, material="
         raise ValueError("min_fill must be a number") from e
     if not np.isfinite(mf) or not 0.0 < mf <= 4.0:
         raise ValueError("min_fill must be finite and in (0, 4]")
-    every = _sample._integer(record_every, "record_every")
-    cap = _sample._integer(record_capacity, "record_capacity")
+    every = selection.integer(record_every, "record_every")
+    cap = selection.integer(record_capacity, "record_capacity")
     if every < 0 or cap < 0:
         raise ValueError("record_every and record_capacity must not be negative")
     if cap * pts.shape[0] * 12 > MAX_HISTORY_BYTES:
         raise ValueError(f"a history of {cap} frames of {pts.shape[0]} tracers takes more than 2^31 bytes")
-    sel = _sample.select_args(fields=(), material=material, objects=objects)
-    return {"points": pts, "min_fill": mf, "record_every": every, "record_capacity": cap, "material": sel["material"],
-            "objects": sel["objects"]}
+    mat, ids = selection.parse(material, objects)
+    return {"points": pts, "min_fill": mf, "record_every": every, "record_capacity": cap, "material": mat, "objects": ids}
 
 
 def tracers_config(config):
@@ -87,14 +87,9 @@ def tracers_config(config):
     plus "recordEvery" (default 1), "minFill" (default 0.2) and "objects".  Returns {"points", "min_fill", "record_every",
     "objects"} -- keyword arguments of `set_tracers` except for the capacity, which the run decides -- or None when the key is
     absent.  A misspelt key or a bad value raises ValueError."""
-    spec = config.get_cfg("tracers")
+    spec = selection.config_object(config, "tracers", CONFIG_KEYS)
     if spec is None:
         return None
-    if not isinstance(spec, dict):
-        raise ValueError('"tracers" must be an object')
-    unknown = set(spec) - set(CONFIG_KEYS)
-    if unknown:
-        raise ValueError(f'"tracers": unknown key(s) {sorted(unknown)}')
     if ("points" in spec) == ("lattice" in spec):
         raise ValueError('"tracers": give either points or lattice')
     try:
@@ -257,7 +252,7 @@ def set_tracers(ps, points, min_fill=0.2, record_every=0, record_capacity=0, mat
                                   "have to travel with the halo")
     p = _lib.SphTracerParams()
     p.min_fill, p.record_every, p.record_capacity = a["min_fill"], a["record_every"], a["record_capacity"]
-    p.select = _sample.make_select({"material": a["material"], "objects": a["objects"]})
+    selection.fill(p.select, a["material"], a["objects"])
     pts = a["points"]
     ps._call("sph_tracers_set", pts.ctypes.data_as(C.c_void_p), pts.shape[0], C.byref(p))
     return Tracers(ps, pts.shape[0], a["record_every"], a["record_capacity"])
@@ -267,6 +262,6 @@ def clear_tracers(ps) -> Tracers:
     from . import _lib
     p = _lib.SphTracerParams()
     p.min_fill = 0.2
-    p.select = _sample.make_select({"material": -1, "objects": []})
+    selection.fill(p.select, -1, [])
     ps._call("sph_tracers_set", None, 0, C.byref(p))
     return Tracers(ps, 0, 0, 0)
