@@ -54,7 +54,7 @@ DevView sph_view(const SphContext* c) {
     d.x0_cold = c->x0_cold; d.rigid_rest_cm = c->rigid_rest_cm; d.polar_fb = c->dyn_count ? c->dyn_count + 3 : nullptr;
     d.m_eps = c->df.m_eps;
     d.stg = c->stg; d.gat = c->gat; d.kbuf = reinterpret_cast<float*>(c->gat);
-    d.m_u = c->m_uniform; d.write_sg = 0; d.write_k = 0;
+    d.m_u = sphs_uniform_mass(c->ss); d.write_sg = 0; d.write_k = 0;
     d.whx = p.wall_hi[0]; d.why = p.wall_hi[1]; d.whz = p.wall_hi[2];
     d.fuse_advect = 0; d.store_acc = 1; d.df_bpart = nullptr;   // per launch: launch_brick_cfg fills them from its SweepArgs
     d.gate = (c->df_epoch && c->opt_df_runahead) ? c->df_gate : nullptr;   // (without run-ahead no body is ever enqueued past convergence)
@@ -84,7 +84,7 @@ __global__ void k_read_cells(const int* __restrict__ cell_end, CellIdx16 ix, int
 int sph_check_device_flags(SphContext* c) {
     if (c->h_pinned && ((volatile int*)c->h_pinned)[16]) {
         ((volatile int*)c->h_pinned)[16] = 0;
-        c->sorted = c->have_prefix = c->have_keys = false;
+        sphs_device_error(c->ss);
         sph_invalidate_lists(c);
         sphd_records_moved(c->dv);
         return sph_fail(c, SPH_E_STATE, "sort: a scan tile never saw a predecessor's total (k_scan_fused's bounded wait ran out), or a fast sort met a rank outside the arrays; "
@@ -130,7 +130,7 @@ static void kin_pose(const SphKinematicMotion& m, double t, KinPose64* out) {
 
 // per object: particle counts and the bounding box of the rest positions, from one download of (x_0, flags); synchronises
 static int sph_obj_info(SphContext* c) {
-    if (c->obj_info_valid) return 0;
+    if (sphs_obj_info_current(c->ss)) return 0;
     const int no = c->p.n_objects;
     if (!c->obj_info) {
         c->obj_info = new (std::nothrow) SphContext::ObjInfo[no > 0 ? no : 1];
@@ -162,7 +162,7 @@ static int sph_obj_info(SphContext* c) {
             }
         }
     }
-    c->obj_info_valid = true;
+    sphs_obj_info_read(c->ss);
     return 0;
 }
 
@@ -223,7 +223,7 @@ static void kin_poses_at(const SphContext* c, double t, KinPoses* P) {
 // [padding, domain - padding] (returns SPH_E_INVALID with the message set; the caller enqueues *n_run steps and hands the code on).
 static int kin_admit(SphContext* c, int n_steps, int* n_run) {
     *n_run = 0;
-    if (!c->obj_info_valid) {   // x_0 / ids / flags were uploaded since sph_kinematic_set (a restart): look again
+    if (!sphs_obj_info_current(c->ss)) {   // x_0 / ids / flags were uploaded since sph_kinematic_set (a restart): look again
         int rc = sph_obj_info(c);
         for (int k = 0; k < c->n_kin && !rc; ++k) rc = kin_check_object(c, "kinematic step", c->kin[k].object_id);
         if (rc) return rc;
@@ -290,6 +290,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     }
     SphContext* c = new SphContext();
     memset(c, 0, sizeof(*c));
+    sphs_init(c->ss);
     c->p = *params;
     c->device = device;
     c->N = params->n_particles;
@@ -402,10 +403,9 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
         sph_destroy(c);
         return rc;
     }
-    c->n_dyn_host = -1;  // unknown until material / is_dynamic are uploaded
     c->rigid_fx_exp = 30;
     sph_invalidate_lists(c);
-    c->opt_uniform = -1; c->uniform_state = -1; c->m_uniform = 0.0f;  // SPH_OPT_UNIFORM_FLUID: auto
+    c->opt_uniform = -1;  // SPH_OPT_UNIFORM_FLUID: auto
     c->opt_variant = SPH_VAR_DEFAULT;
     if (const char* e = getenv("SPH_KERNEL_VARIANT")) { const int v = atoi(e) & 31; c->opt_variant = variant_mask_ok(v) ? v : SPH_VAR_DEFAULT; }  // A/B aid: the default mask of every context of this process
     memset(&c->df_stats, 0, sizeof(c->df_stats));
@@ -451,18 +451,18 @@ int32_t sph_destroy(SphContext* c) {
 int32_t sph_set_option(SphContext* c, int32_t option, int32_t value) {
     if (!c) return SPH_E_INVALID;
     switch (option) {
-        case SPH_OPT_GATHER_IMPL: if (value < 0 || value > 1) return sph_fail(c, SPH_E_INVALID, "gather impl must be 0 or 1"); c->opt_gather_impl = value; c->uniform_state = -1; return 0;
+        case SPH_OPT_GATHER_IMPL: if (value < 0 || value > 1) return sph_fail(c, SPH_E_INVALID, "gather impl must be 0 or 1"); c->opt_gather_impl = value; sphs_option_changed(c->ss, option); return 0;
         case SPH_OPT_TIMING: c->opt_timing = value > 0 ? value : 0; c->timing_phase = 0; return 0;
         case SPH_OPT_FUSED_STEP: c->opt_fused = value ? 1 : 0; return 0;
         case SPH_OPT_BRICK_SHAPE: if (value < 0 || value > 1) return sph_fail(c, SPH_E_INVALID, "brick shape must be 0 (adaptive height) or 1 (fixed 4x2x4)"); c->opt_brick_shape = value; sph_invalidate_lists(c); return 0;
-        case SPH_OPT_NO_DYNAMIC_SOLIDS: c->opt_no_dynamic = value ? 1 : 0; c->n_dyn_host = -1; c->uniform_state = -1; return 0;
+        case SPH_OPT_NO_DYNAMIC_SOLIDS: c->opt_no_dynamic = value ? 1 : 0; sphs_option_changed(c->ss, option); return 0;
         case SPH_OPT_DEBUG_ABLATE:
 #ifndef SPH_PROFILE
             if (value != 0) return sph_fail(c, SPH_E_INVALID, "section ablation exists only in the profiling build (python -m sph_taichi_amd.build --profile; bench.py --ablate loads it)");
 #endif
             c->opt_ablate = value;
             return 0;
-        case SPH_OPT_SLAB_DROP_OUTSIDE: c->opt_drop_outside = value ? 1 : 0; c->uniform_state = -1; return 0;
+        case SPH_OPT_SLAB_DROP_OUTSIDE: c->opt_drop_outside = value ? 1 : 0; sphs_option_changed(c->ss, option); return 0;
         case SPH_OPT_SORT_BY_PID: c->opt_sort_by_pid = value ? 1 : 0; return 0;
         case SPH_OPT_RIGID_BATCH: c->opt_rigid_batch = value ? 1 : 0; return 0;
         case SPH_OPT_EXACT_MATH: c->opt_exact_math = value ? 1 : 0; sph_invalidate_lists(c); return 0;
@@ -472,7 +472,7 @@ int32_t sph_set_option(SphContext* c, int32_t option, int32_t value) {
             c->opt_variant = value < 0 ? SPH_VAR_DEFAULT : value;
             sph_invalidate_lists(c);
             return 0;
-        case SPH_OPT_UNIFORM_FLUID: if (value < -1 || value > 1) return sph_fail(c, SPH_E_INVALID, "uniform-fluid option must be -1, 0 or 1"); c->opt_uniform = value; c->uniform_state = -1; return 0;
+        case SPH_OPT_UNIFORM_FLUID: if (value < -1 || value > 1) return sph_fail(c, SPH_E_INVALID, "uniform-fluid option must be -1, 0 or 1"); c->opt_uniform = value; sphs_option_changed(c->ss, option); return 0;
         case SPH_OPT_RIGID_SUMS_FROM_X0: c->opt_rigid_x0 = value ? 1 : 0; return 0;
         case SPH_OPT_PURE_FLUID_INSTANCE:
             if (value < 0 || value > 2) return sph_fail(c, SPH_E_INVALID, "pure-fluid instance option must be 0, 1 or 2");
@@ -499,10 +499,10 @@ int32_t sph_get_option(const SphContext* c, int32_t option, int32_t* value) {
         case SPH_OPT_RIGID_BATCH: *value = c->opt_rigid_batch; return 0;
         // the EFFECTIVE state: exact-math instances exist for the uniform-fluid step only (sph_hip.h); a scene found not to
         // be one runs the general sweeps with v_rsq / v_rcp whatever was requested, and an A/B must be able to see that
-        case SPH_OPT_EXACT_MATH: *value = (c->opt_exact_math && c->uniform_state != 0) ? 1 : 0; return 0;
+        case SPH_OPT_EXACT_MATH: *value = (c->opt_exact_math && (sphs_uniform(c->ss) || !sphs_uniform_decided(c->ss))) ? 1 : 0; return 0;
         case SPH_OPT_KERNEL_VARIANT: *value = c->opt_variant; return 0;
         case SPH_OPT_DF_RUNAHEAD: *value = c->opt_df_runahead; return 0;
-        case SPH_OPT_UNIFORM_FLUID_STATE: *value = c->uniform_state; return 0;
+        case SPH_OPT_UNIFORM_FLUID_STATE: *value = !sphs_uniform_decided(c->ss) ? -1 : sphs_uniform(c->ss) ? 1 : 0; return 0;
         case SPH_OPT_RIGID_SUMS_FROM_X0: *value = c->opt_rigid_x0; return 0;
         case SPH_OPT_PURE_FLUID_INSTANCE: *value = c->opt_pure_instance; return 0;
         case SPH_OPT_BRICK_RECORDS: *value = c->opt_brick_rec; return 0;
@@ -535,11 +535,8 @@ int32_t sph_set_dt(SphContext* c, float dt) {
 int32_t sph_set_particle_count(SphContext* c, int32_t n) {
     if (!c || n < 0 || n > c->cap) return sph_fail(c, SPH_E_INVALID, "particle count out of range");
     c->N = n;
-    c->n_dyn_host = -1;
-    c->obj_info_valid = false;
-    sph_forget_pure_fluid(c);
+    sphs_count_set(c->ss);
     sphd_set_changed(c->dv);
-    c->have_keys = c->have_prefix = false;
     return 0;
 }
 
@@ -560,7 +557,7 @@ int32_t sph_upload(SphContext* c, int32_t field, const void* host, size_t bytes)
     SPH_HIP(c, hipSetDevice(c->device));
     if (bytes == 0) return 0;
     if (field == SPH_F_DENSITY || field == SPH_F_PRESSURE) { int rc0 = sph_ensure_aux(c); if (rc0) return rc0; }
-    if (field == SPH_F_ACCELERATION) c->acc_partial = false;
+    if (field == SPH_F_ACCELERATION) sphs_acc_written_all(c->ss);
     if (field == SPH_F_RIGID_REST_CM) {
         SPH_HIP(c, hipMemcpyAsync(c->rigid_rest_cm, host, bytes, hipMemcpyHostToDevice, c->stream));
         SPH_HIP(c, hipStreamSynchronize(c->stream));
@@ -571,11 +568,7 @@ int32_t sph_upload(SphContext* c, int32_t field, const void* host, size_t bytes)
     if (rc) return rc;
     sphd_records_moved(c->dv);   // records overwritten from the host: the next sort is the general one
     SPH_HIP(c, hipStreamSynchronize(c->stream));  // host buffer is only borrowed for the call
-    if (field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC || field == SPH_F_DENSITY) c->n_dyn_host = -1;  // (density: the scale of the rigid sums)
-    if (field == SPH_F_MATERIAL || field == SPH_F_M || field == SPH_F_M_V) c->uniform_state = -1;
-    if (field == SPH_F_X) c->have_keys = c->have_prefix = false;
-    if (field == SPH_F_X_0 || field == SPH_F_OBJECT_ID || field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC || field == SPH_F_PID)
-        c->obj_info_valid = false;
+    sphs_field_uploaded(c->ss, field);
     return 0;
 }
 
@@ -585,7 +578,7 @@ int32_t sph_download(SphContext* c, int32_t field, void* host, size_t bytes) {
     if (bytes != field_bytes(c, field)) return sph_fail(c, SPH_E_INVALID, "sph_download: size mismatch");
     SPH_HIP(c, hipSetDevice(c->device));
     if (bytes == 0) return 0;
-    if (field == SPH_F_ACCELERATION && c->acc_partial)
+    if (field == SPH_F_ACCELERATION && !sphs_acc_complete(c->ss))
         return sph_fail(c, SPH_E_STATE, "sph_download(acceleration): the last sph_slab_forces consumed the interior particles' accelerations "
                                         "in its fused finish and did not write them out (stale values would be returned); call "
                                         "sph_compute_non_pressure_forces + sph_compute_pressure_forces, or run with SPH_OPT_FUSED_STEP 0");
@@ -604,14 +597,14 @@ int32_t sph_download(SphContext* c, int32_t field, void* host, size_t bytes) {
 
 // number (and current-order list) of dynamic rigid particles; refreshed lazily
 static int refresh_dyn(SphContext* c) {
-    if (c->n_dyn_host >= 0) return 0;
-    if (c->opt_no_dynamic) { c->n_dyn_host = 0; return 0; }  // the host vouches: no dynamic solids anywhere
+    if (sphs_dyn_known(c->ss)) return 0;
+    if (c->opt_no_dynamic) { sphs_dyn_counted(c->ss, 0); return 0; }  // the host vouches: no dynamic solids anywhere
     int rc = sphk_build_dyn_list(c);
     if (rc) return rc;
     int nr[2] = {0, 0};
     SPH_HIP(c, hipMemcpyAsync(nr, c->dyn_count, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(c, hipStreamSynchronize(c->stream));
-    c->n_dyn_host = nr[0];
+    sphs_dyn_counted(c->ss, nr[0]);
     // Scale of the fixed-point shape-matching sums: n terms of at most m_V0 rho_max L^2 (L = twice the domain's largest
     // extent, a generous bound for |x|, |x - cm| and |x_0 - cm_rest|) must stay below 2^62.
     float rho_max;
@@ -634,8 +627,7 @@ static int refresh_dyn(SphContext* c) {
 static int update_grid_id(SphContext* c, bool allow_fast) {
     int rc = sphk_hash_histogram(c, allow_fast);
     if (rc) return rc;
-    c->have_keys = true;
-    c->have_prefix = false;
+    sphs_hashed(c->ss);
     return 0;
 }
 
@@ -646,16 +638,16 @@ int32_t sph_update_grid_id(SphContext* c) {
 
 int32_t sph_prefix_sum(SphContext* c) {
     ENTER(c);
-    if (!c->have_keys) return sph_fail(c, SPH_E_STATE, "sph_prefix_sum before sph_update_grid_id");
+    if (!sphs_can_scan(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_prefix_sum before sph_update_grid_id");
     int rc = sphk_scan(c);
     if (rc) return rc;
-    c->have_prefix = true;
+    sphs_scanned(c->ss);
     return 0;
 }
 
 static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets = nullptr) {
-    if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_counting_sort before sph_prefix_sum");
-    const bool recount = c->n_dyn_host < 0;
+    if (!sphs_can_scatter(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_counting_sort before sph_prefix_sum");
+    const bool recount = !sphs_dyn_known(c->ss);
     int rc = refresh_dyn(c);
     if (rc) return rc;
     // (the fast hash pass zeroes the dynamic-solid counter, as the place kernel does behind this point on the general path)
@@ -663,8 +655,7 @@ static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_
     rc = sphk_sort_scatter(c, sort_acc, deliver_offsets);
     if (rc) return rc;
     c->in_off = 0;         // the scatter writes the other set from record 0
-    c->have_keys = false;  // the histogram offsets are consumed
-    c->sorted = true;
+    sphs_scattered(c->ss);
     return 0;
 }
 
@@ -684,7 +675,7 @@ int32_t sph_initialize_particle_system(SphContext* c) {
 }
 
 static int need_sorted(SphContext* c, const char* who) {
-    if (!c->sorted || !c->have_prefix) {
+    if (!sphs_neighbours_ready(c->ss)) {
         snprintf(c->err, sizeof(c->err), "%s needs the neighbour structure: call sph_initialize_particle_system first", who);
         return SPH_E_STATE;
     }
@@ -709,7 +700,7 @@ int32_t sph_compute_non_pressure_forces(SphContext* c) {
     int rc = need_sorted(c, "sph_compute_non_pressure_forces");
     rc = rc ? rc : sph_ensure_aux(c);
     rc = rc ? rc : sphk_gather(c, GM_NONPRESSURE);
-    if (!rc) c->acc_partial = false;   // every particle's acceleration has been (re)written
+    if (!rc) sphs_acc_written_all(c->ss);   // every particle's acceleration has been (re)written
     return rc;
 }
 
@@ -747,7 +738,7 @@ int32_t sph_solve_constraints(SphContext* c, int32_t object_id, float* R_out) {
     if (rc) return rc;
     if (R_out) {
         float tmp[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
-        if (c->n_dyn_host > 0) {
+        if (sph_n_dyn(c) > 0) {
             SPH_HIP(c, hipMemcpyAsync(tmp, c->rigid_R, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
             SPH_HIP(c, hipStreamSynchronize(c->stream));
         }
@@ -808,10 +799,10 @@ static int uniform_fluid(SphContext* c) {
     // (a slab rank with dynamic solids computes forces on its first ghost layer too, whose neighbours in the outer
     // ghost layer get no stg / gat records from the density sweep: general path there)
     if (c->opt_uniform == 0 || c->opt_gather_impl != 1 || (c->opt_drop_outside && !c->opt_no_dynamic)) {
-        c->uniform_state = 0;
+        sphs_uniform_ruled_out(c->ss);
         return 0;
     }
-    if (c->uniform_state >= 0) return 0;
+    if (sphs_uniform_decided(c->ss)) return 0;
     return sphk_check_uniform_fluid(c);
 }
 
@@ -820,7 +811,7 @@ static int uniform_fluid(SphContext* c) {
 // decision's check kernel -- launched only when the particle set changed -- reads mass and m_V of FLUID particles and writes
 // the staging buffer; the boundary-volume sweep writes m_V of dynamic SOLID particles and reads no staging.)
 static int density_phase(SphContext* c) {
-    int rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;
+    int rc = sph_n_dyn(c) > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;
     rc = rc ? rc : uniform_fluid(c);
     return rc ? rc : sphk_gather(c, GM_DENSITY_EOS);
 }
@@ -838,7 +829,7 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
         // stg / gat copies), so each fluid target is integrated right in the sweep's finish and the streaming advect
         // kernel disappears.  Dynamic rigid particles collect coupling reactions from many workgroups during the sweep:
         // they are integrated afterwards, by a kernel over their (short) list.
-        const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && !c->opt_drop_outside &&
+        const bool fuse = sphs_uniform(c->ss) && sphd_one_gather_wcsph(c->dv) && !c->opt_drop_outside &&
                           c->opt_gather_impl == 1 && c->N > 0;
         SweepArgs force;
         force.fuse_advect = fuse;
@@ -847,7 +838,7 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
         if (rc) return rc;
         fused_advect = fuse;
     } else {
-        rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
+        rc = sph_n_dyn(c) > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
         rc = rc ? rc : sphk_gather(c, GM_DENSITY);
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
@@ -862,7 +853,7 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
     if (fused_advect) return sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, true);   // (the dynamic solids' advect rides in its first kernel)
     rc = sphk_advect(c, true);
     if (rc) return rc;
-    if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }
+    if (sph_n_dyn(c) > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }
     return 0;
 }
 
@@ -897,8 +888,7 @@ int32_t sph_slab_set_window(SphContext* c, int32_t origin_x, int32_t nx) {
     c->next_heads_zero = false;
     sph_invalidate_lists(c);
     sphd_records_moved(c->dv);
-    c->have_keys = c->have_prefix = c->sorted = false;
-    c->n_dyn_host = -1;
+    sphs_window_changed(c->ss);
     return 0;
 }
 
@@ -935,7 +925,7 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         kin_rc = kin_admit(c, n_steps, &n_steps);
         if (kin_rc && kin_rc != SPH_E_INVALID) return kin_rc;
     }
-    if (n_steps > 0) c->acc_partial = false;   // the call's last step writes every acceleration out
+    if (n_steps > 0) sphs_acc_written_all(c->ss);   // the call's last step writes every acceleration out
     for (int it = 0; it < n_steps; ++it) {
         const double t_end = c->sim_time + (double)c->p.dt;
         hipEvent_t* ev = nullptr;   // SPH_OPT_TIMING k: every k-th step carries the five events
@@ -976,7 +966,7 @@ int32_t sph_get_particle_count(SphContext* c, int32_t* n) {
 int32_t sph_layer_offsets(SphContext* c, const int32_t* layers, int32_t n, int32_t* out) {
     ENTER(c);
     if (!layers || !out || n < 0) return SPH_E_INVALID;
-    if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_layer_offsets needs the prefix sum");
+    if (!sphs_cell_table_ready(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_layer_offsets needs the prefix sum");
     const int per_layer = c->p.grid_num[1] * c->p.grid_num[2];
     for (int k = 0; k < n; ++k)
         if (layers[k] < 0 || layers[k] > c->p.grid_num[0]) return sph_fail(c, SPH_E_INVALID, "layer out of range");
@@ -1018,7 +1008,7 @@ int32_t sph_layer_offsets_begin(SphContext* c, const int32_t* layers, int32_t n)
     ENTER(c);
     c->off_stamp_pending = false;   // (this path delivers through k_read_cells + ev_off)
     if (!layers || n < 0 || n > 16) return SPH_E_INVALID;
-    if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_layer_offsets_begin needs the prefix sum");
+    if (!sphs_cell_table_ready(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_layer_offsets_begin needs the prefix sum");
     CellIdx16 ix;
     int rc0 = layer_offset_cells(c, layers, n, &ix);
     if (rc0) return rc0;
@@ -1065,17 +1055,14 @@ int32_t sph_select_range(SphContext* c, int32_t first, int32_t count) {
     if (first < 0 || count < 0 || first + count > c->in_off + c->N) return sph_fail(c, SPH_E_INVALID, "sph_select_range: out of range");
     c->in_off += first;
     c->N = count;
-    sph_forget_pure_fluid(c);
+    sphs_range_selected(c->ss);
     sphd_set_changed(c->dv);
-    c->have_keys = c->have_prefix = c->sorted = false;
-    c->n_dyn_host = -1;
     return 0;
 }
 
 int32_t sph_truncate(SphContext* c, int32_t n) {
     if (!c || n < 0 || n > c->N) return sph_fail(c, SPH_E_INVALID, "sph_truncate: out of range");
-    if (n != c->N && !c->opt_no_dynamic) c->n_dyn_host = -1;  // the sort's list skipped the dropped strays: recount
-    if (n != c->N) sph_forget_pure_fluid(c);   // (a truncate + append that restores N may bring solids in)
+    sphs_truncated(c->ss, n != c->N, c->opt_no_dynamic != 0);
     sphd_records_moved(c->dv);
     c->N = n;
     return 0;
@@ -1104,12 +1091,9 @@ int32_t sph_append_records(SphContext* c, const void* src, int32_t count) {
     SPH_HIP(c, hipMemcpyAsync(c->vf[c->cur] + o, s + b, b, hipMemcpyDeviceToDevice, c->stream));
     SPH_HIP(c, hipMemcpyAsync(c->aux[c->cur] + o, s + 2 * b, b, hipMemcpyDeviceToDevice, c->stream));
     c->N += count;
-    if (c->opt_uniform != 1) c->uniform_state = -1;  // arrivals are unchecked unless the caller vouches for them
-    sph_forget_pure_fluid(c);   // ... and vouching is for a uniform fluid MASS only: arrivals may be solids
+    sphs_appended(c->ss, c->opt_uniform == 1);
     sph_invalidate_lists(c);
     sphd_records_moved(c->dv);
-    c->have_keys = c->have_prefix = c->sorted = false;
-    c->n_dyn_host = -1;
     return 0;
 }
 
@@ -1132,7 +1116,7 @@ int32_t sph_get_timings(SphContext* c, SphTimings* out) {
 int32_t sph_get_stats(SphContext* c, SphStats* out) {
     ENTER(c);
     if (!out) return SPH_E_INVALID;
-    if (!c->have_prefix) return sph_fail(c, SPH_E_STATE, "sph_get_stats needs a sorted state (run a step first)");
+    if (!sphs_cell_table_ready(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_get_stats needs a sorted state (run a step first)");
     int rc = sphk_stats(c, out);   // synchronises
     return rc ? rc : sph_check_device_flags(c);
 }
@@ -1235,7 +1219,7 @@ int32_t sph_slab_forces(SphContext* c, int32_t bl_lo, int32_t bl_hi, int32_t br_
     // interior: overlaps with the exchange; with the one-gather sweep its finish integrates its own targets (see
     // step_sweeps), so that afterwards only the two boundary ranges -- exactly the packed ranges -- are left to advect
     // (ghost records are not advected at all: the exchange replaces them)
-    const bool fuse = c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv) && c->opt_no_dynamic;
+    const bool fuse = sphs_uniform(c->ss) && sphd_one_gather_wcsph(c->dv) && c->opt_no_dynamic;
     // (an interior target's acceleration is consumed by the advect in the same finish and by nobody else -- the packers
     // read the BOUNDARY sets' -- so, as inside sph_step, it is not written out: 16 B per particle and step less)
     SweepArgs interior;
@@ -1243,12 +1227,12 @@ int32_t sph_slab_forces(SphContext* c, int32_t bl_lo, int32_t bl_hi, int32_t br_
     interior.fuse_advect = fuse;
     interior.store_acc = !fuse;
     rc = sphk_gather_layers(c, GM_FORCE_FUSED, interior);
-    c->acc_partial = fuse;
+    sphs_acc_interior_kept(c->ss, fuse);
     if (rc) return rc;
     if (!no_boundary) SPH_HIP(c, hipStreamWaitEvent(c->stream, c->ev_pack, 0));  // the packers read what the advect overwrites
     hipEvent_t* ev = c->slab_ev_open ? c->ev[c->ev_used] : nullptr;
     if (ev) SPH_HIP(c, hipEventRecord(ev[3], c->stream));  // force = interior sweep (+ the wait for the side stream)
-    if (c->n_dyn_host != 0) { rc = sphk_fold_coupling(c); if (rc) return rc; }  // both force launches have joined: reactions -> accelerations
+    if (sph_n_dyn(c) != 0) { rc = sphk_fold_coupling(c); if (rc) return rc; }  // both force launches have joined: reactions -> accelerations
     if (fuse) {
         // (in a slab only HALO+1 layers wide the two packed ranges overlap: advect their union once)
         const int a0 = firstL, a1 = firstL + nL, b0 = firstR, b1 = firstR + nR;
@@ -1486,7 +1470,7 @@ int32_t sph_dfsph_pressure_solve(SphContext* c) {
 
 // one step of DFSPHSolver between the sort and the kinematic poses (step_loop)
 static int dfsph_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic, bool) {
-    int rc = c->n_dyn_host > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
+    int rc = sph_n_dyn(c) > 0 ? sphk_gather(c, GM_BVOL_DYNAMIC) : 0;   // sph_base.py:265
     // DFSPHSolver.substep (DFSPH.py:400-408)
     rc = rc ? rc : sphk_gather(c, GM_DF_DENSITY);
     rc = rc ? rc : sphk_gather(c, GM_DF_FACTOR);
@@ -1500,7 +1484,7 @@ static int dfsph_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_id
     if (ev) SPH_HIP(c, hipEventRecord(ev[3], c->stream));
     rc = sphk_df_advect(c, true);                                // advect + enforce_boundary_3D(fluid)
     if (rc) return rc;
-    if (c->n_dyn_host > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }  // solve_rigid_body()  sph_base.py:247-260
+    if (sph_n_dyn(c) > 0) { rc = sphk_rigid_solve_all(c, dynamic_ids, n_dynamic, false); if (rc) return rc; }  // solve_rigid_body()  sph_base.py:247-260
     c->df_stats.steps++;
     return 0;
 }

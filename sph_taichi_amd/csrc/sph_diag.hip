@@ -201,7 +201,7 @@ int32_t sph_diag_reduce(SphContext* c) {
         snprintf(c->err, sizeof(c->err), "sph_diag_reduce: %d objects, the per-block row table holds %d", c->p.n_objects, SPH_DIAG_MAX_OBJECTS);
         return SPH_E_INVALID;
     }
-    if (c->acc_partial) return sph_fail(c, SPH_E_STATE, "sph_diag_reduce: the last sph_slab_forces did not write every acceleration out (see sph_download)");
+    if (!sphs_acc_complete(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_diag_reduce: the last sph_slab_forces did not write every acceleration out (see sph_download)");
     if (int rc = diag_state(c)) return rc;
     if (int rc = sph_ensure_aux(c)) return rc;   // density / pressure of a fused step live in eos2 until somebody asks
     const SphLive in = sph_live(c);

@@ -833,7 +833,7 @@ __global__ __launch_bounds__(TPB, (brick_waves_per_simd<MODE, VAR>())) void k_ga
     constexpr bool HAS_W = !mode_reads_list<MODE>();
     constexpr bool V_GROUPS = (VAR & SPH_VAR_GROUPS) != 0 && !mode_reads_list<MODE>();
     constexpr bool V_MFMA = (VAR & SPH_VAR_MFMA) != 0 && V_GROUPS && MODE == GM_DENSITY_EOS;  // the filter on the matrix pipe
-    // A context WITHOUT ANY SOLID particle (checked on the device: SphContext::pure_fluid): every m_V_j is m_V0 BIT FOR BIT, so the
+    // A context WITHOUT ANY SOLID particle (checked on the device: sphs_pure_fluid): every m_V_j is m_V0 BIT FOR BIT, so the
     // density pair term takes it from a register instead of the tile -- one LDS read per hit less, the tile's m_V array is
     // not written -- and computes exactly what it computed before (the same fma with the same operand values: results are
     // bit-identical, unlike a form that would scale the sum of W once).  Chosen by the launcher, not a user-visible bit.
@@ -1553,10 +1553,10 @@ __global__ __launch_bounds__(TPB) void k_fold_coupling(DevView d, const int* __r
 }
 
 int sphk_fold_coupling(SphContext* c) {
-    if (c->opt_no_dynamic || c->n_dyn_host == 0 || c->N <= 0) return 0;
+    if (c->opt_no_dynamic || sph_n_dyn(c) == 0 || c->N <= 0) return 0;
     DevView d = sph_view(c);
-    const bool have_list = c->n_dyn_host > 0;
-    const int n = have_list ? c->n_dyn_host : c->N;
+    const bool have_list = sph_n_dyn(c) > 0;
+    const int n = have_list ? sph_n_dyn(c) : c->N;
     hipLaunchKernelGGL(k_fold_coupling, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, have_list ? c->dyn_list : nullptr, 0, n);
     SPH_LAUNCH_CHECK(c);
     return 0;
@@ -1566,7 +1566,7 @@ int sphk_fold_coupling(SphContext* c) {
 // the halo packers advance the boundary layers' records right behind the boundary force launch and need those
 // particles' reactions -- complete by then, sph_slab_forces -- while the interior launch is still scattering to others)
 int sphk_fold_coupling_range(SphContext* c, int first, int count, hipStream_t st) {
-    if (c->opt_no_dynamic || c->n_dyn_host == 0 || count <= 0) return 0;
+    if (c->opt_no_dynamic || sph_n_dyn(c) == 0 || count <= 0) return 0;
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_fold_coupling, dim3((count + TPB - 1) / TPB), dim3(TPB), 0, st, d, (const int*)nullptr, first, count);
     SPH_LAUNCH_CHECK(c);
@@ -1673,7 +1673,7 @@ static int launch_brick_cfg(SphContext* c, const SweepArgs& a) {
     d.fuse_advect = a.fuse_advect;
     d.store_acc = a.store_acc || !a.fuse_advect;  // (only the fused advect has consumed the acceleration it does not store)
     d.df_bpart = a.collect_bpart ? c->df_bpart : nullptr;
-    if (MODE == GM_DENSITY_EOS) { d.tgt_lo = c->tgt_layers[0]; d.tgt_hi = c->tgt_layers[1]; d.write_sg = c->uniform_state == 1; }
+    if (MODE == GM_DENSITY_EOS) { d.tgt_lo = c->tgt_layers[0]; d.tgt_hi = c->tgt_layers[1]; d.write_sg = sphs_uniform(c->ss); }
     if (MODE == GM_DF_DENSITY) d.write_sg = 1;
     if (mode_is_df_vdiv<MODE>()) d.write_k = 1;
     if (MODE == GM_FORCE_FUSED || MODE == GM_FORCE_FUSED_U) { d.tgt_lo = c->tgt_layers[2]; d.tgt_hi = c->tgt_layers[3]; }
@@ -1777,7 +1777,7 @@ static int launch_brick(SphContext* c, const SweepArgs& a) {
 template <int MODE>
 static int sweep_done(SphContext* c, const SweepArgs& a, int rc) {
     if (rc) return rc;
-    if (MODE == GM_DENSITY_EOS) sphd_lists_written(c->dv, c->uniform_state == 1 ? 1 : 0);
+    if (MODE == GM_DENSITY_EOS) sphd_lists_written(c->dv, sphs_uniform(c->ss) ? 1 : 0);
     if (MODE == GM_DF_DENSITY) sphd_lists_written(c->dv, 2);
     if (mode_is_df_vdiv<MODE>() && a.collect_bpart) sphd_bpart_written(c->dv);  // every listed brick leaves its partial of the density error
     if (MODE == GM_DF_DENSITY_CHANGE) sphd_k_written(c->dv, 1);
@@ -1794,7 +1794,7 @@ int sphk_gather_layers(SphContext* c, int mode, const SweepArgs& args) {
     if (mode != GM_FORCE_FUSED || c->opt_gather_impl == 0) return sph_fail(c, SPH_E_INVALID, "layer-restricted sweeps need the brick force kernel");
     SweepArgs a = args;
     if (a.hi < a.lo) a.hi = a.lo;
-    if (c->uniform_state == 1 && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
+    if (sphs_uniform(c->ss) && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
     return sweep_done<GM_FORCE_FUSED>(c, a, launch_brick<GM_FORCE_FUSED>(c, a));
 }
 
@@ -1831,7 +1831,7 @@ static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a);
 int sphk_gather(SphContext* c, int mode, const SweepArgs& a) {
     int rc = gather_dispatch(c, mode, a);
     // sweeps that scatter two-way coupling reactions (WCSPH.py:66-68, DFSPH.py:313, 389-390) are followed by the fold
-    if (!rc && c->n_dyn_host != 0 && (mode == GM_PRESSURE || mode == GM_FORCE_FUSED || mode == GM_DF_DIV_ITER || mode == GM_DF_PRESSURE_ITER))
+    if (!rc && sph_n_dyn(c) != 0 && (mode == GM_PRESSURE || mode == GM_FORCE_FUSED || mode == GM_DF_DIV_ITER || mode == GM_DF_PRESSURE_ITER))
         rc = sphk_fold_coupling(c);
     return rc;
 }
@@ -1845,10 +1845,10 @@ static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a) {
     switch (mode) {
         case GM_BVOL_STATIC: return launch_simple<GM_BVOL_STATIC>(c, nullptr, c->N);  // init only
         case GM_BVOL_DYNAMIC: {
-            if (c->n_dyn_host <= 0) return 0;
+            if (sph_n_dyn(c) <= 0) return 0;
             DevView d = sph_view(c);
-            hipLaunchKernelGGL(k_gather_bvol_split<GM_BVOL_DYNAMIC>, dim3((c->n_dyn_host * 16 + TPB - 1) / TPB), dim3(TPB), 0,
-                               c->stream, d, c->dyn_list, c->n_dyn_host);
+            hipLaunchKernelGGL(k_gather_bvol_split<GM_BVOL_DYNAMIC>, dim3((sph_n_dyn(c) * 16 + TPB - 1) / TPB), dim3(TPB), 0,
+                               c->stream, d, c->dyn_list, sph_n_dyn(c));
             SPH_LAUNCH_CHECK(c);
             return 0;
         }
@@ -1859,7 +1859,7 @@ static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a) {
         case GM_FORCE_FUSED:
             // one gather per pair when every fluid particle has the same mass (and the density sweep of this step
             // left its stg / gat records): see SPH_OPT_UNIFORM_FLUID
-            if (c->uniform_state == 1 && c->opt_gather_impl == 1 && brick_ok(c) && sphd_one_gather_wcsph(c->dv) && c->N > 0)
+            if (sphs_uniform(c->ss) && c->opt_gather_impl == 1 && brick_ok(c) && sphd_one_gather_wcsph(c->dv) && c->N > 0)
                 return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
             return launch_sweep<GM_FORCE_FUSED>(c, a);
         case GM_DF_DENSITY: return launch_df<GM_DF_DENSITY>(c, a);

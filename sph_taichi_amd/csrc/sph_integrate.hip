@@ -1016,10 +1016,10 @@ int sphk_advect_range(SphContext* c, int first, int count) {
 
 int sphk_advect_dyn_list(SphContext* c) {
     sph_invalidate_lists(c);
-    if (c->n_dyn_host <= 0) return 0;
+    if (sph_n_dyn(c) <= 0) return 0;
     DevView d = sph_view(c);
-    hipLaunchKernelGGL(k_advect_list, dim3((c->n_dyn_host + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, wall_hi(c), c->dyn_list,
-                       c->n_dyn_host);
+    hipLaunchKernelGGL(k_advect_list, dim3((sph_n_dyn(c) + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, wall_hi(c), c->dyn_list,
+                       sph_n_dyn(c));
     SPH_LAUNCH_CHECK(c);
     return 0;
 }
@@ -1039,9 +1039,9 @@ int sphk_enforce_boundary(SphContext* c, int particle_type) {
     DevView d = sph_view(c);
     if (particle_type == SPH_MATERIAL_SOLID) {
         // only dynamic solids can be hit: run over the dynamic-rigid list
-        if (c->n_dyn_host <= 0) return 0;
-        hipLaunchKernelGGL(k_enforce_boundary, dim3((c->n_dyn_host + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d,
-                           wall_hi(c), particle_type, c->dyn_list, c->n_dyn_host);
+        if (sph_n_dyn(c) <= 0) return 0;
+        hipLaunchKernelGGL(k_enforce_boundary, dim3((sph_n_dyn(c) + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d,
+                           wall_hi(c), particle_type, c->dyn_list, sph_n_dyn(c));
     } else {
         hipLaunchKernelGGL(k_enforce_boundary, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, wall_hi(c),
                            particle_type, (const int*)nullptr, c->N);
@@ -1054,7 +1054,7 @@ int sphk_enforce_boundary(SphContext* c, int particle_type) {
 int sphk_rigid_com(SphContext* c, int object_id, bool to_rest) {
     DevView d = sph_view(c);
     d.rigid_from_x0 = (to_rest && c->opt_rigid_x0) ? 1 : 0;
-    const int n = c->n_dyn_host > 0 ? c->n_dyn_host : 0;
+    const int n = sph_n_dyn(c) > 0 ? sph_n_dyn(c) : 0;
     const int nb = n > 0 ? (n + TPB - 1) / TPB : 1;
     if (nb > c->rigid_part_blocks) return sph_fail(c, SPH_E_NOMEM, "rigid partial-sum buffer too small");
     // n == 0 (no dynamic particle, e.g. the rest cm of a static body): one block of zeros -> 0/0 = NaN like the reference
@@ -1069,9 +1069,9 @@ int sphk_rigid_com(SphContext* c, int object_id, bool to_rest) {
 // solve_constraints (sph_base.py:200-222) without any host round trip: 3 launches, no atomics
 int sphk_rigid_solve(SphContext* c, int object_id) {
     sph_invalidate_lists(c);
-    if (c->n_dyn_host <= 0) return 0;
+    if (sph_n_dyn(c) <= 0) return 0;
     DevView d = sph_view(c);
-    const int n = c->n_dyn_host, nb = (n + TPB - 1) / TPB;
+    const int n = sph_n_dyn(c), nb = (n + TPB - 1) / TPB;
     if (nb > c->rigid_part_blocks) return sph_fail(c, SPH_E_NOMEM, "rigid partial-sum buffer too small");
     hipLaunchKernelGGL(k_rigid_sum, dim3(nb), dim3(TPB), 0, c->stream, d, c->dyn_list, n, object_id, (fx_t*)c->rigid_part);
     SPH_LAUNCH_CHECK(c);
@@ -1087,8 +1087,8 @@ int sphk_rigid_solve(SphContext* c, int object_id) {
 // of them when they fit the batch (<= 16 bodies, per-body rows of partials), else body by body.  advect_first: the
 // advect of the dynamic rigid particles (what sphk_advect_dyn_list does) happens here too, inside the first kernel
 int sphk_rigid_solve_all(SphContext* c, const int* ids, int n_ids, bool advect_first) {
-    if (c->n_dyn_host <= 0 || n_ids <= 0) return advect_first ? sphk_advect_dyn_list(c) : 0;
-    const int n = c->n_dyn_host, nb = (n + TPB - 1) / TPB;
+    if (sph_n_dyn(c) <= 0 || n_ids <= 0) return advect_first ? sphk_advect_dyn_list(c) : 0;
+    const int n = sph_n_dyn(c), nb = (n + TPB - 1) / TPB;
     if (!c->opt_rigid_batch || n_ids > SPH_MAX_BATCH_BODIES || (long long)nb * n_ids > c->rigid_part_blocks) {
         if (advect_first) { int rc = sphk_advect_dyn_list(c); if (rc) return rc; }
         for (int k = 0; k < n_ids; ++k) {
@@ -1171,7 +1171,7 @@ int sphk_build_dyn_list(SphContext* c) {
 int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, double* out) {
     DevView d = sph_view(c);
     d.rigid_from_x0 = c->opt_rigid_x0;   // (the host sets the option around the mode-0 sums of a restart only)
-    const int n = c->n_dyn_host;
+    const int n = sph_n_dyn(c);
     const int nb = n > 0 ? (n + TPB - 1) / TPB : 0;
     if (nb > c->rigid_part_blocks) return sph_fail(c, SPH_E_NOMEM, "rigid partial-sum buffer too small");
     if (nb > 0) {
@@ -1187,7 +1187,7 @@ int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, dou
 int sphk_rigid_apply16(SphContext* c, int object_id, const double* sums, int mode) {
     sph_invalidate_lists(c);
     DevView d = sph_view(c);
-    const int n = c->n_dyn_host;
+    const int n = sph_n_dyn(c);
     const int nb = (mode == 1 && n > 0) ? (n + TPB - 1) / TPB : 1;
     hipLaunchKernelGGL(k_rigid_apply_sums, dim3(nb), dim3(TPB), 0, c->stream, d, c->dyn_list, n, object_id, sums, mode,
                        c->rigid_R);
@@ -1281,10 +1281,7 @@ int sphk_df_density_error(SphContext* c, float offset, float* out_host) {
 }
 
 int sphk_check_uniform_fluid(SphContext* c) {
-    c->uniform_state = 0;
-    c->pure_fluid = 0;
-    c->pure_fluid_n = -1;
-    c->m_uniform = 0.0f;
+    sphs_uniform_check_begun(c->ss);
     if (c->N <= 0) return 0;
     DevView d = sph_view(c);
     unsigned* out = reinterpret_cast<unsigned*>(c->stage);  // 16 bytes of the staging buffer
@@ -1297,12 +1294,11 @@ int sphk_check_uniform_fluid(SphContext* c) {
     SPH_HIP(c, hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     SPH_HIP(c, hipStreamSynchronize(c->stream));
     if (h[3] > 0 && h[0] == h[1] && h[2] == 0) {
-        memcpy(&c->m_uniform, &h[0], sizeof(float));
-        c->uniform_state = c->m_uniform > 0.0f ? 1 : 0;
-        // every particle is a fluid particle (and h[2] == 0 above: every fluid m_V is m_V0 bit for bit) => no solid at all.
+        float m;
+        memcpy(&m, &h[0], sizeof(float));
+        // h[3] fluid particles, and h[2] == 0 above: every fluid m_V is m_V0 bit for bit, so h[3] == N means no solid at all.
         // (whether the launcher USES the verdict is SPH_OPT_PURE_FLUID_INSTANCE: the A/B switch of the instance it selects)
-        c->pure_fluid = (c->uniform_state == 1 && h[3] == (unsigned)c->N) ? 1 : 0;
-        c->pure_fluid_n = c->N;
+        sphs_uniform_checked(c->ss, m, h[3], c->N);
     }
     return 0;
 }

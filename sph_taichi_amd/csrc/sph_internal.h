@@ -22,6 +22,16 @@
 
 #include "../../include/sph_hip.h"
 #include "sph_derived.h"
+#include "sph_setstate.h"
+
+// sph_setstate.h includes nothing, so it mirrors the ids its tables speak of: they are the public ones
+static_assert(SPHS_F_OBJECT_ID == (int)SPH_F_OBJECT_ID && SPHS_F_X == (int)SPH_F_X && SPHS_F_X_0 == (int)SPH_F_X_0 &&
+              SPHS_F_M_V == (int)SPH_F_M_V && SPHS_F_M == (int)SPH_F_M && SPHS_F_DENSITY == (int)SPH_F_DENSITY &&
+              SPHS_F_MATERIAL == (int)SPH_F_MATERIAL && SPHS_F_IS_DYNAMIC == (int)SPH_F_IS_DYNAMIC && SPHS_F_PID == (int)SPH_F_PID,
+              "sph_setstate.h: field ids differ from sph_hip.h");
+static_assert(SPHS_OPT_GATHER_IMPL == (int)SPH_OPT_GATHER_IMPL && SPHS_OPT_NO_DYNAMIC_SOLIDS == (int)SPH_OPT_NO_DYNAMIC_SOLIDS &&
+              SPHS_OPT_SLAB_DROP_OUTSIDE == (int)SPH_OPT_SLAB_DROP_OUTSIDE && SPHS_OPT_UNIFORM_FLUID == (int)SPH_OPT_UNIFORM_FLUID,
+              "sph_setstate.h: option ids differ from sph_hip.h");
 
 #define SPH_MATERIAL_SOLID 0  // particle_system.py:30
 #define SPH_MATERIAL_FLUID 1  // particle_system.py:31
@@ -161,14 +171,13 @@ struct SphContext {
     float* rigid_rest_cm;  // [n_objects*3]
     int* dyn_list;     // [cap] sorted-order indices of dynamic rigid particles
     int* dyn_count;    // device counter
-    int n_dyn_host;    // number of dynamic rigid particles (constant; counted at upload)
-    int rigid_fx_exp;  // S of the fixed-point shape-matching sums: set with n_dyn_host from the count, the largest body density and the domain size
+    int rigid_fx_exp;  // S of the fixed-point shape-matching sums: set with the count of dynamic rigid particles (sph_n_dyn), the largest body density and the domain size
     double* rigid_part;   // [rigid_part_blocks][16] per-block partial sums of the shape-matching reductions
     int rigid_part_blocks;
     float* rigid_R;    // [12] cm[3] + R[9]
     void* stage;       // upload/download staging, cap*16 bytes (>= G*4)
     size_t stage_bytes;
-    bool have_keys, have_prefix, sorted;
+    SphSetState ss;     // what the host knows about the particle set and how far the sort pipeline has got: sph_setstate.h
     SphDerived dv;      // which derived buffers (lists, partition, column records, staging, k_j, ...) are current: sph_derived.h
     double* h_df_err;   // pinned, device-visible: result of compute_density_error
     struct DfSlot { float err; int converged; double avg; }* h_df_slot;  // [4] pinned, device-visible: the convergence test of a solver iteration
@@ -192,13 +201,7 @@ struct SphContext {
     int opt_rigid_x0;     // SPH_OPT_RIGID_SUMS_FROM_X0: the rest-cm sums read x_0 (set by the host around the rest cm of a restart)
     int opt_pure_instance;  // SPH_OPT_PURE_FLUID_INSTANCE: 1 (default) = a solid-free single context may run the pure-fluid instances (density, one-gather force)
     int opt_variant;     // SPH_OPT_KERNEL_VARIANT (bit mask of SPH_VAR_*)
-    bool acc_partial;    // sph_slab_forces with the interior advect fused: the interior targets' accelerations were consumed in the
-                         // force finish and never written out; sph_download(ACCELERATION) refuses until something writes them all
     int opt_uniform;     // SPH_OPT_UNIFORM_FLUID: -1 auto, 0 off, 1 check once
-    int uniform_state;   // -1 unknown, 0 the precondition fails, 1 holds (m_uniform valid)
-    int pure_fluid;      // (with uniform_state == 1) the check found no solid particle at all among pure_fluid_n particles:
-    int pure_fluid_n;    //   every m_V is m_V0 bit for bit (single context only: a slab rank's arrivals are never checked)
-    float m_uniform;
     // timing
     hipEvent_t ev[SPH_MAX_TIMED_STEPS][5];
     int ev_used;
@@ -217,7 +220,6 @@ struct SphContext {
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
     SphKinematicMotion kin[SPH_MAX_KINEMATIC];
     struct ObjInfo { int n, n_static; double lo[3], hi[3]; }* obj_info;  // [n_objects] particle counts (all / static solid) and rest AABB (x_0)
-    bool obj_info_valid;    // obj_info describes the current x_0 / object ids / flags (one download: sph_obj_info)
     char err[512];
 };
 
@@ -231,17 +233,10 @@ static inline bool sph_is_slab(const SphContext* c) {
     return c->p.cell_origin[0] != 0 || c->p.cell_origin[1] != 0 || c->p.cell_origin[2] != 0 || c->p.cold_capacity > 0 ||
            c->p.grid_num[0] != c->nx_alloc || c->opt_drop_outside || c->in_off != 0;
 }
-// the particle SET changed (records appended / dropped / re-selected): whatever a device-side check established about it is void
-static inline void sph_forget_pure_fluid(SphContext* c) { c->pure_fluid = 0; c->pure_fluid_n = -1; }
-// May the sweeps of the uniform-fluid step run their pure-fluid instances?  ONE rule for both (density + EOS, one-gather force):
-// the device-side check found no solid among exactly the particles the context holds now (pure_fluid is only ever set by a check
-// of THIS particle set: same count, single context), or the HOST vouches that the whole scene holds no solid particle
-// (SPH_OPT_PURE_FLUID_INSTANCE 2: a slab rank, whose arrivals are never checked; every particle of such a scene keeps
-// m_V = m_V0 bit for bit wherever it lives).  Whatever changes the particle set forgets the verdict (sph_forget_pure_fluid),
-// an upload of material / m / m_V asks for a new check (uniform_state = -1), SPH_OPT_PURE_FLUID_INSTANCE 0 is the A/B switch.
+// the rules of the set state (counts, verdicts, sort stage) are sph_setstate.h's; these are its most frequent readers
+static inline int sph_n_dyn(const SphContext* c) { return sphs_dyn_count(c->ss); }  // dynamic rigid particles; -1: not counted yet
 static inline bool sph_pure_fluid_instances(const SphContext* c) {
-    const bool pure_checked = c->opt_pure_instance == 1 && c->pure_fluid && c->pure_fluid_n == c->N && !c->opt_drop_outside;
-    return c->uniform_state == 1 && (pure_checked || c->opt_pure_instance == 2);
+    return sphs_pure_fluid(c->ss, c->opt_pure_instance, c->N, c->opt_drop_outside != 0);
 }
 // after a host synchronisation: did a device-side error flag rise since the last look (k_scan_fused's bounded wait)?  Marks the
 // sort invalid and returns SPH_E_STATE with the message set; 0 otherwise.
@@ -284,7 +279,7 @@ int sphk_eos(SphContext* c);
 int sph_ensure_aux(SphContext* c);  // materialise density / pressure in aux if the lean density finish left them in eos2
 int sphk_stats(SphContext* c, SphStats* out);  // synchronises
 int sphk_df_convergence_test(SphContext* c, float offset, double eta, int slot);  // device-side compute_density_error + test
-int sphk_check_uniform_fluid(SphContext* c);  // sets uniform_state / m_uniform (synchronises)
+int sphk_check_uniform_fluid(SphContext* c);  // reports the uniform-fluid verdict and the mass (synchronises)
 int sphk_df_density_error(SphContext* c, float offset, float* out_host);
 int sphk_df_density_error_range(SphContext* c, float offset, int first, int count, double* out_host);
 int sphk_df_scale_factor(SphContext* c, float s);
