@@ -186,7 +186,16 @@ enum SphOption {
                                   sph_counting_sort, slab ranks -- is the general one.  0 = the general sort everywhere (A/B).  Same
                                   order, same arrays, bit for bit.  sph_get_option reports the requested value. */,
     SPH_OPT_SORT_FAST_COUNT = 19,   /* read-only: sorts of this context that ran on the fast path ... */
-    SPH_OPT_SORT_GENERAL_COUNT = 20 /* ... and on the general path (both wrap at 2^31) */
+    SPH_OPT_SORT_GENERAL_COUNT = 20, /* ... and on the general path (both wrap at 2^31) */
+    SPH_OPT_SORT_LEAN = 21     /* 1 (default) = a fast sort (SPH_OPT_SORT_FAST) at the head of a step of sph_step moves the persistent id alone, through
+                                  an array of its own, in place of the 16-byte (m, density, pressure, id) record: 40 B per particle each
+                                  way instead of 52.  Taken only on the step whose sweeps leave that record alone -- the fused
+                                  uniform-fluid step under the rule that admits the pure-fluid instances (SPH_OPT_PURE_FLUID_INSTANCE),
+                                  without registered kinematic motions -- where m is one value and density / pressure wait in the
+                                  step's own 8-byte record.  Whoever asks for any of the four words (a download, an upload, an
+                                  observer, a stand-alone call, another kind of sort, a change of the particle set) gets the record
+                                  written back first, once: same arrays, same results, bit for bit.  0 = the record is moved by
+                                  every sort (A/B; profiles/sort_lean_ab.json).  sph_get_option reports the requested value. */
 };
 #define SPH_VAR_GROUPS 1   /* density: all nine runs filtered first (masks in registers), hits emitted centre run / edge runs / corner
                               runs, each group by descending hit count */

@@ -49,7 +49,7 @@ DevView sph_view(const SphContext* c) {
         else d.w_d = 0.0f;
     }
     const int o = c->in_off;
-    d.xm = c->xm[c->cur] + o; d.vf = c->vf[c->cur] + o; d.aux = c->aux[c->cur] + o; d.key = c->key[c->cur] + o;
+    d.xm = c->xm[c->cur] + o; d.vf = c->vf[c->cur] + o; d.aux = c->aux[c->cur] + o; d.key = c->key[c->cur] + o; d.pid = c->pid[c->cur] + o;
     d.eos = c->eos; d.eos2 = reinterpret_cast<float2*>(c->eos); d.acc = c->acc + o; d.acc_fx = c->acc_fx + 3 * (size_t)o; d.cell_end = c->cell_end;
     d.x0_cold = c->x0_cold; d.rigid_rest_cm = c->rigid_rest_cm; d.polar_fb = c->dyn_count ? c->dyn_count + 3 : nullptr;
     d.m_eps = c->df.m_eps;
@@ -307,6 +307,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     c->opt_rigid_batch = 1;
     c->opt_df_fuse_err = 1;
     c->opt_sort_fast = SPH_SORT_FAST_DEFAULT;
+    c->opt_sort_lean = SPH_SORT_LEAN_DEFAULT;
     c->opt_df_runahead = 0;   // measured (r05): running ahead costs 2 % more than the bubbles it removes
     c->opt_exact_math = 0;
     c->opt_rigid_x0 = 0;
@@ -328,6 +329,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
         rc = rc ? rc : alloc_dev(c, (void**)&c->vf[s], cap * 16);
         rc = rc ? rc : alloc_dev(c, (void**)&c->aux[s], cap * 16);
         rc = rc ? rc : alloc_dev(c, (void**)&c->key[s], cap * 4);
+        rc = rc ? rc : alloc_dev(c, (void**)&c->pid[s], cap * 4);
     }
     rc = rc ? rc : alloc_dev(c, (void**)&c->eos, cap * 16);
     rc = rc ? rc : alloc_dev(c, (void**)&c->stg, cap * 16);
@@ -408,6 +410,7 @@ int32_t sph_create(const SphParams* params, int32_t device, void* stream, SphCon
     c->opt_uniform = -1;  // SPH_OPT_UNIFORM_FLUID: auto
     c->opt_variant = SPH_VAR_DEFAULT;
     if (const char* e = getenv("SPH_KERNEL_VARIANT")) { const int v = atoi(e) & 31; c->opt_variant = variant_mask_ok(v) ? v : SPH_VAR_DEFAULT; }  // A/B aid: the default mask of every context of this process
+    if (const char* e = getenv("SPH_SORT_LEAN")) c->opt_sort_lean = atoi(e) ? 1 : 0;  // A/B aid, like the one above: bench.py sets no option of its own
     memset(&c->df_stats, 0, sizeof(c->df_stats));
     c->df.enable_divergence_solver = 1; c->df.m_max_iterations_v = 100; c->df.m_max_iterations = 100;  // DFSPH.py:12-20
     c->df.fluid_particle_num = 0; c->df.m_eps = 1e-5f; c->df.reserved_ = 0.0f; c->df.max_error_V = 0.1; c->df.max_error = 0.05;
@@ -419,7 +422,7 @@ int32_t sph_destroy(SphContext* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->xm[0], c->xm[1], c->vf[0], c->vf[1], c->aux[0], c->aux[1], c->key[0], c->key[1], c->eos, c->stg, c->gat, c->acc,
+    void* ptrs[] = {c->xm[0], c->xm[1], c->vf[0], c->vf[1], c->aux[0], c->aux[1], c->key[0], c->key[1], c->pid[0], c->pid[1], c->eos, c->stg, c->gat, c->acc,
                     c->acc_tmp, c->cell_buf[0], c->cell_buf[1], c->cell_buf[2], c->head_buf[0], c->head_buf[1], c->rank_off, c->idx_unstable, c->scan_status, c->x0_cold, c->color_cold,
                     c->rigid_rest_cm, c->dyn_list, c->dyn_count, c->acc_fx, c->rigid_part, c->rigid_R, c->df_err, c->df_part, c->df_bpart, c->stage, c->glist, c->gcnt, c->brick_list, c->brick_count, c->brick_list2, c->brick_count2, c->brick_rec};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -480,6 +483,7 @@ int32_t sph_set_option(SphContext* c, int32_t option, int32_t value) {
         case SPH_OPT_BRICK_RECORDS: c->opt_brick_rec = value ? 1 : 0; sph_invalidate_lists(c); return 0;
         case SPH_OPT_DF_FUSE_ERROR: c->opt_df_fuse_err = value ? 1 : 0; return 0;
         case SPH_OPT_SORT_FAST: c->opt_sort_fast = value ? 1 : 0; return 0;
+        case SPH_OPT_SORT_LEAN: c->opt_sort_lean = value ? 1 : 0; return 0;
     }
     return sph_fail(c, SPH_E_INVALID, "unknown option");
 }
@@ -508,6 +512,7 @@ int32_t sph_get_option(const SphContext* c, int32_t option, int32_t* value) {
         case SPH_OPT_BRICK_RECORDS: *value = c->opt_brick_rec; return 0;
         case SPH_OPT_DF_FUSE_ERROR: *value = c->opt_df_fuse_err; return 0;
         case SPH_OPT_SORT_FAST: *value = c->opt_sort_fast; return 0;
+        case SPH_OPT_SORT_LEAN: *value = c->opt_sort_lean; return 0;
         case SPH_OPT_SORT_FAST_COUNT: *value = c->n_sort_fast; return 0;
         case SPH_OPT_SORT_GENERAL_COUNT: *value = c->n_sort_general; return 0;
     }
@@ -534,6 +539,8 @@ int32_t sph_set_dt(SphContext* c, float dt) {
 
 int32_t sph_set_particle_count(SphContext* c, int32_t n) {
     if (!c || n < 0 || n > c->cap) return sph_fail(c, SPH_E_INVALID, "particle count out of range");
+    SPH_HIP(c, hipSetDevice(c->device));
+    if (int rc = sph_ensure_pid(c)) return rc;   // ids that live apart from aux describe the records counted so far
     c->N = n;
     sphs_count_set(c->ss);
     sphd_set_changed(c->dv);
@@ -645,14 +652,14 @@ int32_t sph_prefix_sum(SphContext* c) {
     return 0;
 }
 
-static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets = nullptr) {
+static int counting_sort(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets = nullptr, bool aux_dead_in_step = false) {
     if (!sphs_can_scatter(c->ss)) return sph_fail(c, SPH_E_STATE, "sph_counting_sort before sph_prefix_sum");
     const bool recount = !sphs_dyn_known(c->ss);
     int rc = refresh_dyn(c);
     if (rc) return rc;
     // (the fast hash pass zeroes the dynamic-solid counter, as the place kernel does behind this point on the general path)
     if (recount && c->sort_fast_pending) SPH_HIP(c, hipMemsetAsync(c->dyn_count, 0, sizeof(int), c->stream));
-    rc = sphk_sort_scatter(c, sort_acc, deliver_offsets);
+    rc = sphk_sort_scatter(c, sort_acc, deliver_offsets, aux_dead_in_step);
     if (rc) return rc;
     c->in_off = 0;         // the scatter writes the other set from record 0
     sphs_scattered(c->ss);
@@ -859,10 +866,11 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
 
 // hash + scan + scatter without touching aux: for callers that run a density sweep right behind it (nothing can read the
 // stale density / pressure copies the scatter moves in between; the acceleration is dead there too)
-static int sort_no_fold(SphContext* c, const CellIdx16* deliver_offsets = nullptr, bool allow_fast = false) {
+// aux_dead_in_step: the caller's step neither reads nor writes aux before the next sort (step_aux_dead)
+static int sort_no_fold(SphContext* c, const CellIdx16* deliver_offsets = nullptr, bool allow_fast = false, bool aux_dead_in_step = false) {
     int rc = update_grid_id(c, allow_fast && !deliver_offsets);
     rc = rc ? rc : sph_prefix_sum(c);
-    return rc ? rc : counting_sort(c, false, deliver_offsets);
+    return rc ? rc : counting_sort(c, false, deliver_offsets, aux_dead_in_step);
 }
 
 int32_t sph_set_target_layers(SphContext* c, int32_t dlo, int32_t dhi, int32_t flo, int32_t fhi) {
@@ -913,6 +921,17 @@ int32_t sph_sweeps(SphContext* c) {
 // the sort (ev[1] recorded) and the kinematic poses: it records ev[2] and ev[3] of a timed step.
 typedef int (*StepBody)(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids, int32_t n_dynamic, bool last_step);
 
+// Does a step of `body` leave aux alone from its sort to the next one?  Only the fused uniform-fluid WCSPH step does: its density
+// finish keeps (p, rho) in eos2 and its one-gather force sweep reads the staged records -- as brick sweeps: the cell walk of a
+// context beyond their reach reads aux (sph_gather.hip; a sweep that would touch aux after all asks for the fold itself,
+// gather_dispatch).  The in-step consumers of aux between two sorts are the
+// kinematic poses (the id of a registered object's particles) and the rigid solve (ids and densities of dynamic solids): both
+// need solids, which the pure-fluid rule of the lean scatter excludes, and registered motions are excluded here by name.  The
+// tracers read xm / vf and the cell array only.
+static bool step_aux_dead(const SphContext* c, StepBody body) {
+    return body == step_sweeps && c->opt_fused && c->opt_gather_impl == 1 && sphk_brick_sweeps_reach(c) && c->n_kin == 0;
+}
+
 static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
     if (n_steps < 0 || n_dynamic < 0 || (n_dynamic > 0 && !dynamic_ids)) {
         snprintf(c->err, sizeof(c->err), "%s: bad arguments", who);
@@ -930,7 +949,7 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         const double t_end = c->sim_time + (double)c->p.dt;
         hipEvent_t* ev = nullptr;   // SPH_OPT_TIMING k: every k-th step carries the five events
         rc = timed_step_begin(c, &ev);
-        rc = rc ? rc : sort_no_fold(c, nullptr, true);   // ps.initialize_particle_system()   sph_base.py:264
+        rc = rc ? rc : sort_no_fold(c, nullptr, true, step_aux_dead(c, body));   // ps.initialize_particle_system()   sph_base.py:264
         if (rc) return rc;
         if (ev) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
         if (c->tracers) {   // a registered tracer set advances with v(t_k) through the cell array of this sort (sph_hip.h, "Passive tracers")
@@ -1053,6 +1072,7 @@ int32_t sph_layer_offsets_end(SphContext* c, int32_t* out, int32_t n) {
 int32_t sph_select_range(SphContext* c, int32_t first, int32_t count) {
     ENTER(c);
     if (first < 0 || count < 0 || first + count > c->in_off + c->N) return sph_fail(c, SPH_E_INVALID, "sph_select_range: out of range");
+    if (int rc = sph_ensure_pid(c)) return rc;   // (the pid array is indexed from the old first record)
     c->in_off += first;
     c->N = count;
     sphs_range_selected(c->ss);
@@ -1072,6 +1092,7 @@ int32_t sph_pack_range(SphContext* c, int32_t first, int32_t count, void* dst) {
     ENTER(c);
     if (first < 0 || count < 0 || first + count > c->N || (count > 0 && !dst)) return sph_fail(c, SPH_E_INVALID, "sph_pack_range: out of range");
     if (count == 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;
     const size_t b = (size_t)count * 16, o = (size_t)c->in_off + first;
     char* d = (char*)dst;
     SPH_HIP(c, hipMemcpyAsync(d, c->xm[c->cur] + o, b, hipMemcpyDeviceToDevice, c->stream));
@@ -1085,6 +1106,7 @@ int32_t sph_append_records(SphContext* c, const void* src, int32_t count) {
     if (count < 0 || (count > 0 && !src)) return SPH_E_INVALID;
     if (c->in_off + c->N + count > c->cap) return sph_fail(c, SPH_E_NOMEM, "sph_append_records: capacity exceeded");
     if (count == 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the arrivals bring whole records: the ones already here get theirs back first
     const size_t b = (size_t)count * 16, o = (size_t)c->in_off + c->N;
     const char* s = (const char*)src;
     SPH_HIP(c, hipMemcpyAsync(c->xm[c->cur] + o, s, b, hipMemcpyDeviceToDevice, c->stream));

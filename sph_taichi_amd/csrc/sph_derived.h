@@ -16,11 +16,19 @@
 //                         change; a sort or a new record selection (other indices) ends that.
 //       df_bpart_valid    set and consumed inside one solver iteration, with nothing in between.
 //       brick_count_zero  describes the counter, not the particles.
+//       pid_apart         says where the ids ARE; it also survives sphd_set_changed() and a sort (see the lean scatter below).
 //   * The fast sort (sph_sort.hip: stayers ranked from the previous order) reads the previous sort's keys and cell array as
 //     the description of the CURRENT order.  That holds from a sort until records are moved, inserted, dropped, re-selected
 //     or overwritten from the host, or the grid window changes (sphd_records_moved); positions drifting under the advect do
 //     not end it -- that drift is what the next sort measures.  A sort that hashed strays into the virtual cell G leaves an
 //     order the fast path has no rule for.
+//   * The LEAN scatter (SPH_OPT_SORT_LEAN: sph_sort.hip, k_stable_scatter_fast's lean forms) moves the persistent id through
+//     an array of its own and leaves the aux record behind: on a pure-fluid uniform step m is one known value, density and
+//     pressure live in eos2, and the id is the record's only live word.  From the first lean scatter on, "the ids live
+//     apart": aux of the current order holds nothing current, and only the fold (sph_ensure_aux: m, density, pressure and
+//     id written back as one record) ends that.  Nothing else does: not a sort, not a change of the set, not an option --
+//     whoever reads or writes aux, re-bases or resizes the set, or sorts any other way asks for the fold FIRST
+//     (sphd_aux_needs_fold / sphd_pid_apart), so a forgotten demand leaves a pending fold, never a lost id.
 #pragma once
 
 // identity of a brick partition: the cut rule and the target x-layer ranges it was cut for
@@ -52,6 +60,7 @@ struct SphDerived {
     bool aux_stale;         // density / pressure of the fluid live in eos2 (lean density finish), not yet in aux
     bool brick_count_zero;  // brick_count is zero (hash kernel) and no list has been built into it since
     bool order_from_sort;   // the current record order is a sort's output under the current key and cell arrays, without strays in cell G
+    bool pid_apart;         // the persistent ids of the current order live in the pid array (lean scatter), not in aux
 };
 
 // ---- events ----------------------------------------------------------------------------------------------------------
@@ -94,7 +103,10 @@ static inline void sphd_records_written(SphDerived& s, const SphPartKey& key) { 
 static inline void sphd_k_written(SphDerived& s, int kind) { s.k_kind = kind; }
 static inline void sphd_bpart_written(SphDerived& s) { s.df_bpart_valid = true; }
 static inline void sphd_bpart_consumed(SphDerived& s) { s.df_bpart_valid = false; }
-static inline void sphd_aux_folded(SphDerived& s) { s.aux_stale = false; }
+// the fold wrote the whole aux record of every particle: (m, density, pressure, id) are where every reader looks for them
+static inline void sphd_aux_folded(SphDerived& s) { s.aux_stale = false; s.pid_apart = false; }
+// a lean scatter has been enqueued: it moved the ids through the pid array and left aux behind
+static inline void sphd_scattered_lean(SphDerived& s) { s.pid_apart = true; }
 static inline void sphd_count_zeroed(SphDerived& s, bool zero) { s.brick_count_zero = zero; }
 
 // ---- questions -------------------------------------------------------------------------------------------------------
@@ -110,9 +122,22 @@ static inline bool sphd_one_gather_df(const SphDerived& s, int k_kind) { return 
 static inline bool sphd_stats_have_lists(const SphDerived& s) { return s.gcnt_written; }
 static inline bool sphd_bpart_ready(const SphDerived& s) { return s.df_bpart_valid; }
 static inline bool sphd_aux_in_eos2(const SphDerived& s) { return s.aux_stale; }
+static inline bool sphd_pid_apart(const SphDerived& s) { return s.pid_apart; }
+// does aux lack anything a reader may look for in it (density / pressure still in eos2, the ids still apart)?
+static inline bool sphd_aux_needs_fold(const SphDerived& s) { return s.aux_stale || s.pid_apart; }
 static inline bool sphd_count_is_zero(const SphDerived& s) { return s.brick_count_zero; }
 // may the next sort rank stayers from the previous order (SPH_OPT_SORT_FAST)?  Only under the reference's intra-cell order
 // (previous index) and without the virtual cell
 static inline bool sphd_sort_fast_usable(const SphDerived& s, bool opt_fast, bool sort_by_pid, bool drop_outside) {
     return opt_fast && s.order_from_sort && !sort_by_pid && !drop_outside;
 }
+// may this fast scatter be a lean one (SPH_OPT_SORT_LEAN)?  pure_uniform: the rule that admits the pure-fluid instances of
+// both sweeps holds, so m is the one uniform mass; aux_dead_in_step: the step this sort heads is the fused uniform-fluid
+// WCSPH step, whose sweeps neither read nor write aux, and no in-step consumer of aux is armed; sort_acc: the caller wants
+// the accelerations moved too (a stand-alone sort: its caller may read any field next).  The fast sort already excludes
+// sort_by_pid and the virtual cell.
+static inline bool sphd_sort_lean_usable(const SphDerived&, bool opt_lean, bool fast, bool pure_uniform, bool aux_dead_in_step, bool sort_acc) {
+    return opt_lean && fast && pure_uniform && aux_dead_in_step && !sort_acc;
+}
+// 0: the scatter moves aux; 1: lean, the ids come from the pid array; 2: lean, the ids come from aux.w (entering)
+static inline int sphd_scatter_form(const SphDerived& s, bool lean) { return !lean ? 0 : s.pid_apart ? 1 : 2; }

@@ -275,6 +275,7 @@ int32_t sph_export_select(SphContext* c, const SphExportParams* p) {
     if (p->fields & (SPH_EXPORT_DENSITY | SPH_EXPORT_PRESSURE))
         if (int rc = sph_ensure_aux(c)) return rc;   // density / pressure of a fused step live in eos2 until somebody asks
     SphExport* s = c->exporter;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
     const SphLive in = sph_live(c);
     hipLaunchKernelGGL(k_export_clear, dim3(s->table_len / ETPB), dim3(ETPB), 0, c->stream, s->table, s->table_len, s->counters);
     SPH_LAUNCH_CHECK(c);

@@ -1584,12 +1584,34 @@ __global__ __launch_bounds__(TPB) void k_aux_from_eos2(DevView d) {
     a[2] = e.x;
 }
 
+// ... and, behind a lean scatter (sph_sort.hip), the WHOLE record: the one uniform mass, density / pressure (from eos2 when
+// EOS2; else the words aux holds stay -- nobody has computed newer ones for this order), and the id from the pid array.  Every
+// particle of a lean run is a fluid particle of that mass (sphd_sort_lean_usable).
+template <bool EOS2>
+__global__ __launch_bounds__(TPB) void k_aux_from_pid(DevView d) {
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= d.N) return;
+    const float w = __int_as_float(d.pid[i]);
+    if (EOS2) {
+        const float2 e = d.eos2[i];
+        d.aux[i] = make_float4(d.m_u, e.y, e.x, w);
+    } else {
+        float* a = reinterpret_cast<float*>(&d.aux[i]);
+        a[0] = d.m_u;
+        a[3] = w;
+    }
+}
+
 int sph_ensure_aux(SphContext* c) {
-    if (!sphd_aux_in_eos2(c->dv)) return 0;
+    if (!sphd_aux_needs_fold(c->dv)) return 0;
+    const bool eos2 = sphd_aux_in_eos2(c->dv), apart = sphd_pid_apart(c->dv);
     sphd_aux_folded(c->dv);
     if (c->N <= 0) return 0;
     DevView d = sph_view(c);
-    hipLaunchKernelGGL(k_aux_from_eos2, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d);
+    const dim3 grid((c->N + TPB - 1) / TPB);
+    if (!apart) hipLaunchKernelGGL(k_aux_from_eos2, grid, dim3(TPB), 0, c->stream, d);
+    else if (eos2) hipLaunchKernelGGL(k_aux_from_pid<true>, grid, dim3(TPB), 0, c->stream, d);
+    else hipLaunchKernelGGL(k_aux_from_pid<false>, grid, dim3(TPB), 0, c->stream, d);
     SPH_LAUNCH_CHECK(c);
     return 0;
 }
@@ -1635,6 +1657,8 @@ static int launch_simple(SphContext* c, const int* list, int n) {
 static bool brick_ok(const SphContext* c) {
     return c->glist_shift > 0 && c->p.grid_num[2] <= SPH_BRICK_MAX_NZ;
 }
+
+bool sphk_brick_sweeps_reach(const SphContext* c) { return brick_ok(c); }
 
 // identity of a partition: footprint, cut rule, limits (the target ranges complete the key)
 static int brick_partition_id(const SphContext* c) {
@@ -1792,6 +1816,7 @@ int sphk_gather_layers(SphContext* c, int mode, const SweepArgs& args) {
         return sph_fail(c, SPH_E_INVALID, "a slab rank needs the brick sweeps, and this context is beyond their reach (capacity > 16.7 M particles "
                                           "or more than 1000 cell layers in z): cut the domain into more slabs");
     if (mode != GM_FORCE_FUSED || c->opt_gather_impl == 0) return sph_fail(c, SPH_E_INVALID, "layer-restricted sweeps need the brick force kernel");
+    if (int rc = sph_ensure_pid(c)) return rc;   // (a slab rank never sorts lean; a context that did and became one gets its aux back)
     SweepArgs a = args;
     if (a.hi < a.lo) a.hi = a.lo;
     if (sphs_uniform(c->ss) && sphd_one_gather_wcsph(c->dv)) return sweep_done<GM_FORCE_FUSED_U>(c, a, launch_brick<GM_FORCE_FUSED_U>(c, a));
@@ -1837,6 +1862,13 @@ int sphk_gather(SphContext* c, int mode, const SweepArgs& a) {
 }
 
 static int gather_dispatch(SphContext* c, int mode, const SweepArgs& a) {
+    // ids apart from aux (lean scatter): only the pair of sweeps of the fused uniform-fluid step runs without the record -- the
+    // density sweep of the brick path when it writes the staged records (write_sg), the force sweep when it takes its one-gather form
+    if (sphd_pid_apart(c->dv)) {
+        const bool brick_u = sphs_uniform(c->ss) && c->opt_gather_impl == 1 && brick_ok(c) && c->N > 0;
+        const bool alone = (mode == GM_DENSITY_EOS && brick_u) || (mode == GM_FORCE_FUSED && brick_u && sphd_one_gather_wcsph(c->dv));
+        if (!alone) { int rc = sph_ensure_aux(c); if (rc) return rc; }
+    }
     // every sweep but the fused step's own pair reads or rewrites density / pressure in aux
     if (sphd_aux_in_eos2(c->dv) && mode != GM_DENSITY_EOS && mode != GM_FORCE_FUSED && mode != GM_BVOL_STATIC && mode != GM_BVOL_DYNAMIC) {
         int rc = sph_ensure_aux(c);

@@ -1026,6 +1026,7 @@ int sphk_advect_dyn_list(SphContext* c) {
 
 int sphk_pack_advected(SphContext* c, int first, int count, void* dst, hipStream_t st) {
     if (count <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_pack_advected, dim3((count + TPB - 1) / TPB), dim3(TPB), 0, st, d, wall_hi(c), first, count,
                        (float4*)dst);
@@ -1052,6 +1053,7 @@ int sphk_enforce_boundary(SphContext* c, int particle_type) {
 
 // cm of object -> rigid_R[0..2] (and rigid_rest_cm[object] when to_rest)
 int sphk_rigid_com(SphContext* c, int object_id, bool to_rest) {
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     d.rigid_from_x0 = (to_rest && c->opt_rigid_x0) ? 1 : 0;
     const int n = sph_n_dyn(c) > 0 ? sph_n_dyn(c) : 0;
@@ -1070,6 +1072,7 @@ int sphk_rigid_com(SphContext* c, int object_id, bool to_rest) {
 int sphk_rigid_solve(SphContext* c, int object_id) {
     sph_invalidate_lists(c);
     if (sph_n_dyn(c) <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     const int n = sph_n_dyn(c), nb = (n + TPB - 1) / TPB;
     if (nb > c->rigid_part_blocks) return sph_fail(c, SPH_E_NOMEM, "rigid partial-sum buffer too small");
@@ -1099,6 +1102,7 @@ int sphk_rigid_solve_all(SphContext* c, const int* ids, int n_ids, bool advect_f
         return 0;
     }
     sph_invalidate_lists(c);
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     BodyIds b;
     b.n = n_ids;
@@ -1116,6 +1120,7 @@ int sphk_rigid_solve_all(SphContext* c, const int* ids, int n_ids, bool advect_f
 
 int sphk_extract(SphContext* c, int field, void* dst) {
     if (c->N <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_extract, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, field, c->color_cold, dst);
     SPH_LAUNCH_CHECK(c);
@@ -1125,6 +1130,7 @@ int sphk_extract(SphContext* c, int field, void* dst) {
 int sphk_insert(SphContext* c, int field, const void* src) {
     if (field == SPH_F_X || field == SPH_F_MATERIAL || field == SPH_F_IS_DYNAMIC) sph_invalidate_lists(c);
     if (c->N <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads the id in aux and writes aux fields
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_insert, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, field, c->x0_cold,
                        c->color_cold, src);
@@ -1134,6 +1140,7 @@ int sphk_insert(SphContext* c, int field, const void* src) {
 
 int sphk_rest_records(SphContext* c, float4* dst) {
     if (c->N <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_rest_records, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, dst);
     SPH_LAUNCH_CHECK(c);
@@ -1144,6 +1151,7 @@ int sphk_rest_records(SphContext* c, float4* dst) {
 int sphk_kinematic_apply(SphContext* c, const KinPoses& poses) {
     sph_invalidate_lists(c);
     if (c->N <= 0 || poses.n <= 0) return 0;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     hipLaunchKernelGGL(k_kinematic_apply, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, poses);
     SPH_LAUNCH_CHECK(c);
@@ -1160,6 +1168,7 @@ int sphk_init_pid(SphContext* c) {
 int sphk_build_dyn_list(SphContext* c) {
     SPH_HIP(c, hipMemsetAsync(c->dyn_count, 0, 2 * sizeof(int), c->stream));
     if (c->N > 0) {
+        if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
         DevView d = sph_view(c);
         hipLaunchKernelGGL(k_build_dyn_list, dim3((c->N + TPB - 1) / TPB), dim3(TPB), 0, c->stream, d, c->dyn_list,
                            c->dyn_count);
@@ -1169,6 +1178,7 @@ int sphk_build_dyn_list(SphContext* c) {
 }
 
 int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, double* out) {
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     d.rigid_from_x0 = c->opt_rigid_x0;   // (the host sets the option around the mode-0 sums of a restart only)
     const int n = sph_n_dyn(c);
@@ -1186,6 +1196,7 @@ int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, dou
 
 int sphk_rigid_apply16(SphContext* c, int object_id, const double* sums, int mode) {
     sph_invalidate_lists(c);
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernel reads aux
     DevView d = sph_view(c);
     const int n = sph_n_dyn(c);
     const int nb = (mode == 1 && n > 0) ? (n + TPB - 1) / TPB : 1;
@@ -1281,6 +1292,7 @@ int sphk_df_density_error(SphContext* c, float offset, float* out_host) {
 }
 
 int sphk_check_uniform_fluid(SphContext* c) {
+    if (int rc = sph_ensure_pid(c)) return rc;   // the fold writes the mass of the verdict this check is about to forget; the kernel reads aux
     sphs_uniform_check_begun(c->ss);
     if (c->N <= 0) return 0;
     DevView d = sph_view(c);

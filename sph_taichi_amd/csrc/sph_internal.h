@@ -10,6 +10,7 @@
 //   glist[24 << glist_shift bytes] u16, gcnt[cap] u8  neighbour lists: entry r of particle i at (r >> 2) << glist_shift | i * 8 | (r & 3) * 2
 //   acc[cap] float4 = (ax, ay, az, 0)
 //   key[cap] int    = grid_ids                        ping-pong
+//   pid[cap] int    = persistent id                   ping-pong; current only while the ids live apart from aux (lean scatter, sph_derived.h)
 //   x0_cold [3*cap] f32, color_cold [3*cap] i32       indexed by pid, never moved
 //   cell_end[G] int = inclusive prefix of the cell histogram (= the reference's
 //                     grid_particles_num after PrefixSumExecutor.run)
@@ -39,6 +40,7 @@ static_assert(SPHS_OPT_GATHER_IMPL == (int)SPH_OPT_GATHER_IMPL && SPHS_OPT_NO_DY
 #define SPH_GLIST_ROWS 96  // list entries allocated per particle (24 groups of four); lists up to LISTCAP = 95 entries (developed dam-break flows reach 58, profiles/archive/r03i)
 #define SPH_DF_ERR_BLOCKS 512
 #define SPH_SORT_FAST_DEFAULT 1   // SPH_OPT_SORT_FAST when the caller does not choose (profiles/sort_fast_ab.json)
+#define SPH_SORT_LEAN_DEFAULT 1   // SPH_OPT_SORT_LEAN when the caller does not choose (profiles/sort_lean_ab.json)
 #define SPH_VAR_PURE_INTERNAL 64   // not a user bit (sph_set_option refuses masks above 63): the pure-fluid instances of the density sweep and of the one-gather force sweep
 #define SPH_VAR_DEFAULT (SPH_VAR_GROUPS | SPH_VAR_FORCE_BF | SPH_VAR_DEEP)  // SPH_OPT_KERNEL_VARIANT when the caller does not choose: the fastest rows of profiles/archive/r03f_variants_partition_x_emission.json (density) and r02g_variants_force.json (force)
 
@@ -86,6 +88,7 @@ struct DevView {
     float4* acc;
     long long* acc_fx;  // [3 N] two-way coupling reactions on dynamic rigid particles, 2^32 fixed point (couple_scatter / k_fold_coupling)
     int* key;
+    int* pid;   // the persistent ids of the current order while they live apart from aux (lean scatter); stale otherwise
     int* cell_end;
     const float* x0_cold;
     int* polar_fb;   // counter of solve_constraints() calls that took the Jacobi-SVD fallback (context's dyn_count[3])
@@ -130,6 +133,7 @@ struct SphContext {
     float4* vf[2];
     float4* aux[2];
     int* key[2];
+    int* pid[2];   // persistent ids, moved by the lean scatter in place of the aux record (who is current: sph_derived.h)
     float4* eos;
     float2* eos2; // lean target record (p, rho) of the uniform-fluid WCSPH step (same memory as eos)
     float4* stg;
@@ -149,6 +153,7 @@ struct SphContext {
     bool next_heads_zero;  // head_buf[head_cur ^ 1] is all zero
     bool sort_fast_pending;  // the last hash pass was the fast one: scan and scatter must be too
     int opt_sort_fast;       // SPH_OPT_SORT_FAST
+    int opt_sort_lean;       // SPH_OPT_SORT_LEAN
     int n_sort_fast, n_sort_general;  // sorts run to their end, by path (SPH_OPT_SORT_FAST_COUNT / _GENERAL_COUNT)
     int* rank_off;     // [cap] arbitrary intra-cell offset from the histogram atomics (fast sort: the NEW key of every old index)
     int* idx_unstable; // [cap] (fast sort: next arrival of the same cell, as 1 + old index, at a mover's old index)
@@ -257,10 +262,13 @@ int sph_check_device_flags(SphContext* c);
 // ---- launch entry points implemented in the .hip files --------------------
 int sphk_hash_histogram(SphContext* c, bool allow_fast = false);  // allow_fast: the caller's sort may take the fast path when the derived state permits it
 int sphk_scan(SphContext* c);
-int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets);  // non-null: the place kernel also hands these scanned cells to the host
+// deliver_offsets non-null: the place kernel also hands these scanned cells to the host.  aux_dead_in_step: the caller is the
+// fused uniform-fluid step with no consumer of aux armed -- the scatter may be the lean one (sph_derived.h)
+int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets, bool aux_dead_in_step = false);
 int sphk_rigid_partial16(SphContext* c, int object_id, int first, int count, double* out);
 int sphk_rigid_apply16(SphContext* c, int object_id, const double* sums, int mode);
 int sphk_scatter_rest(SphContext* c, const int* pid_dev, const float* x0_dev, int n);
+bool sphk_brick_sweeps_reach(const SphContext* c);  // sph_gather.hip: the context is within the brick sweeps' limits (else every sweep is the per-particle cell walk)
 struct BrickListArgs;
 int sphk_brick_list_prepare(SphContext* c, BrickListArgs* a, SphPartKey* key);  // sph_gather.hip: what the sort's place kernel needs to build the step's brick list, and the key it will serve
 // What ONE sweep launch is told beyond its mode.  The default value is the plain sweep: the mode's own targets, nothing fused,
@@ -276,7 +284,9 @@ int sphk_gather(SphContext* c, int mode, const SweepArgs& a = SweepArgs());
 int sphk_gather_layers(SphContext* c, int mode, const SweepArgs& a);  // force sweep over the targets of a.lo .. a.hi2 only (slab mode)
 int sphk_pack_advected(SphContext* c, int first, int count, void* dst, hipStream_t st);
 int sphk_eos(SphContext* c);
-int sph_ensure_aux(SphContext* c);  // materialise density / pressure in aux if the lean density finish left them in eos2
+int sph_ensure_aux(SphContext* c);  // materialise density / pressure in aux if the lean density finish left them in eos2, and the whole record if a lean scatter keeps the ids apart
+// ... for whoever reads or writes m or the id in aux, or re-bases / resizes the records, and does not ask for density or pressure
+static inline int sph_ensure_pid(SphContext* c) { return sphd_pid_apart(c->dv) ? sph_ensure_aux(c) : 0; }
 int sphk_stats(SphContext* c, SphStats* out);  // synchronises
 int sphk_df_convergence_test(SphContext* c, float offset, double eta, int slot);  // device-side compute_density_error + test
 int sphk_check_uniform_fluid(SphContext* c);  // reports the uniform-fluid verdict and the mass (synchronises)

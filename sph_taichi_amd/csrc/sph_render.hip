@@ -374,6 +374,7 @@ static int render_alloc(SphContext* c, SphRender* r) {
 
 template <int LAYER>
 int frame_enqueue_layer(SphContext* c, const RenderCam& cam, const FramePlanes& planes, unsigned* big_count, const FrameField& field) {
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
     const SphLive in = sph_live(c);
     int* big_list = reinterpret_cast<int*>(c->stage);          // stage_bytes >= 16 * capacity; the previous layer's large launch is ahead on the stream
     const int big_cap = (int)(c->stage_bytes / 4 < (size_t)0x7fffffff ? c->stage_bytes / 4 : (size_t)0x7fffffff);
@@ -497,6 +498,7 @@ int32_t sph_field_range(SphContext* c, const SphFieldColour* colour, SphFieldRan
     FieldHidden hidden;
     hidden.n = r->cam.n_invisible;
     memcpy(hidden.ids, r->cam.invisible, sizeof(hidden.ids));
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
     const SphLive in = sph_live(c);
     hipLaunchKernelGGL(k_field_range_clear, dim3(1), dim3(64), 0, c->stream, r->range_words);
     SPH_LAUNCH_CHECK(c);

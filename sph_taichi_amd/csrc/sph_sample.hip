@@ -399,6 +399,7 @@ static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad
     g.nodes = nodes;
     g.planes = s->grid;
     if (int rc = sample_clear(c, s->grid, words)) return rc;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
     const SphLive in = sph_live(c);
     if (in.N > 0) {
         const SphWalk w = sph_observe_walk(in.N, STPB, SG_MAX_BLOCKS);
@@ -498,6 +499,7 @@ static int sample_points_run(SphContext* c, const float* xyz, int32_t m, int32_t
     s->pts_copying = true;
     SPH_HIP(c, hipMemcpyAsync(s->pts_buf, s->pts_host, (size_t)3 * m * 4, hipMemcpyHostToDevice, c->stream));
     if (int rc = sample_clear(c, s->pts, (size_t)q.channels * m)) return rc;
+    if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
     const SphLive in = sph_live(c);
     if (in.N > 0) {
         const SphWalk w = sph_observe_walk(in.N, STPB, SP_MAX_BLOCKS);

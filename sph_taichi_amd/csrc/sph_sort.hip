@@ -279,11 +279,16 @@ __device__ __forceinline__ int sph_popc_range(unsigned long long w, int a, int b
 // Fast form of the scatter (rule at the head of this file).  d.key is the OLD key of old index s, d.cell_end the NEW scanned
 // cell array; old_end the previous one.  The brick-list workgroups, the zeroing of the next cell array (and of the next
 // head array), the dyn_list append and SORT_ACC are the general kernel's.
-template <bool SORT_ACC>
+// LEAN (SPH_OPT_SORT_LEAN; when: sphd_sort_lean_usable): on the pure-fluid uniform step the aux record holds one live word, the
+// persistent id -- m is one value, density and pressure live in eos2 -- so the id alone is moved, through the pid arrays:
+// 40 B per particle each way instead of 52.  0: the whole aux record; 1: pid_in -> pid_out; 2: the first lean scatter of a
+// run, which finds the ids in aux.w (it still fetches the record, and stores 4 B).  sph_ensure_aux writes aux back.
+template <bool SORT_ACC, int LEAN>
 __global__ __launch_bounds__(TPB) void k_stable_scatter_fast(DevView d, const int* __restrict__ old_end, const int* __restrict__ key_new,
                                                              const int* __restrict__ head, const int* __restrict__ next,
                                                              float4* __restrict__ xm_out, float4* __restrict__ vf_out,
-                                                             float4* __restrict__ aux_out, int* __restrict__ key_out,
+                                                             float4* __restrict__ aux_out, const int* __restrict__ pid_in,
+                                                             int* __restrict__ pid_out, int* __restrict__ key_out,
                                                              float4* __restrict__ acc_out, int* __restrict__ dyn_list,
                                                              int* __restrict__ dyn_count, int4* __restrict__ zero_dst,
                                                              int4* __restrict__ zero_head, int zero_n4, int* __restrict__ err,
@@ -361,10 +366,11 @@ __global__ __launch_bounds__(TPB) void k_stable_scatter_fast(DevView d, const in
     if ((unsigned)dst >= (unsigned)d.N) { *err = 1; return; }
     const float4 xm = d.xm[s];
     const float4 vf = d.vf[s];
-    const float4 aux = d.aux[s];
     xm_out[dst] = xm;
     vf_out[dst] = vf;
-    aux_out[dst] = aux;
+    if (LEAN == 0) aux_out[dst] = d.aux[s];
+    if (LEAN == 1) pid_out[dst] = pid_in[s];
+    if (LEAN == 2) pid_out[dst] = __float_as_int(d.aux[s].w);
     key_out[dst] = c;
     if (SORT_ACC) acc_out[dst] = d.acc[s];
     if (sph_is_dynamic_rigid(__float_as_int(vf.w))) dyn_list[atomicAdd(dyn_count, 1)] = dst;
@@ -442,8 +448,12 @@ static int sort_scatter_done(SphContext* c, int o, int zeroed, bool sort_acc, bo
     return 0;
 }
 
-int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets) {
+int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_offsets, bool aux_dead_in_step) {
     if (c->N <= 0) return 0;
+    // lean: the ids alone are moved.  Every other scatter moves aux, so ids that live apart are folded back into it first
+    const bool lean = sphd_sort_lean_usable(c->dv, c->opt_sort_lean != 0, c->sort_fast_pending && !deliver_offsets,
+                                            sph_pure_fluid_instances(c), aux_dead_in_step, sort_acc);
+    if (!lean) { int rc0 = sph_ensure_pid(c); if (rc0) return rc0; }
     DevView d = sph_view(c);
     const int nb = (c->N + TPB - 1) / TPB;
     const int o = c->cur ^ 1;
@@ -464,15 +474,14 @@ int sphk_sort_scatter(SphContext* c, bool sort_acc, const CellIdx16* deliver_off
         const int* old_end = c->cell_buf[c->cell_prev];
         const int* head = c->head_buf[c->head_cur];
         int4* zero_head = reinterpret_cast<int4*>(c->head_buf[c->head_cur ^ 1]);
-        if (sort_acc)
-            hipLaunchKernelGGL(k_stable_scatter_fast<true>, dim3(nb + bl.nblocks), dim3(TPB), bl.lds_bytes, c->stream, d, old_end, c->rank_off,
-                               head, c->idx_unstable, c->xm[o], c->vf[o], c->aux[o], c->key[o], c->acc_tmp, c->dyn_list, c->dyn_count,
-                               zero_dst, zero_head, zero_n4, c->scan_err, bl);
-        else
-            hipLaunchKernelGGL(k_stable_scatter_fast<false>, dim3(nb + bl.nblocks), dim3(TPB), bl.lds_bytes, c->stream, d, old_end, c->rank_off,
-                               head, c->idx_unstable, c->xm[o], c->vf[o], c->aux[o], c->key[o], c->acc_tmp, c->dyn_list, c->dyn_count,
-                               zero_dst, zero_head, zero_n4, c->scan_err, bl);
+        const int form = sphd_scatter_form(c->dv, lean);
+        auto kern = sort_acc ? k_stable_scatter_fast<true, 0> : form == 1 ? k_stable_scatter_fast<false, 1>
+                             : form == 2 ? k_stable_scatter_fast<false, 2> : k_stable_scatter_fast<false, 0>;
+        hipLaunchKernelGGL(kern, dim3(nb + bl.nblocks), dim3(TPB), bl.lds_bytes, c->stream, d, old_end, c->rank_off, head, c->idx_unstable,
+                           c->xm[o], c->vf[o], c->aux[o], d.pid, c->pid[o], c->key[o], c->acc_tmp, c->dyn_list, c->dyn_count, zero_dst,
+                           zero_head, zero_n4, c->scan_err, bl);
         SPH_LAUNCH_CHECK(c);
+        if (lean) sphd_scattered_lean(c->dv);
         c->next_heads_zero = true;
         c->sort_fast_pending = false;
         c->n_sort_fast = (c->n_sort_fast + 1) & 0x7fffffff;
