@@ -1005,6 +1005,76 @@ int32_t sph_tracers_download(SphContext* ctx, float* x /*[m][3]*/, float* u /*[m
                              int32_t* wet_steps, int32_t* dry_steps, int32_t m);   /* any pointer may be NULL; synchronises */
 int32_t sph_tracers_history_download(SphContext* ctx, float* xyz /*[frames][m][3]*/, int64_t frames, int32_t m);   /* synchronises */
 
+/* ======================================================================================
+ * Running flow statistics (the reference has none; every Eulerian observer above is of one instant): a context may hold ONE
+ * registered statistics set -- a grid as in "Field sampling" (a volume, or a slice when one n[a] is 1), whose nodes accumulate ON THE
+ * DEVICE, across steps, how often they were wet and the first and second moments of the velocity there: time-mean velocity, RMS
+ * fluctuations, Reynolds stresses, turbulent kinetic energy and intermittency follow on the host from 11 integers per node.
+ * VELOCITY ONLY: grid.fields must be 0 or exactly SPH_SAMPLE_VX | SPH_SAMPLE_VY | SPH_SAMPLE_VZ (both mean the same).  Density and
+ * pressure statistics are out of scope: at the hook below those of a fused step lie in the step's own record in the PRE-sort order,
+ * and materialising them would write particle state.  A sample reads positions, volumes, velocities and flags and nothing else.
+ * THE HOOK: while a set is registered, every step of sph_step / sph_dfsph_step is counted (steps_seen, from 0 at registration, carried
+ * across calls), and step k is SAMPLED iff steps_seen % every == 0 before it is counted.  The sample is enqueued where the tracers
+ * advance: behind the step's sort and before its sweeps, so it is of x(t_k), v(t_k) at the simulated time t_k of the step's
+ * beginning.  Two launches per sampled step on the context's stream, no synchronisation, nothing crosses to the host; in a timed step
+ * (SPH_OPT_TIMING) they fall where the tracer advance falls.  With no set registered (never set, or cleared) both step calls enqueue
+ * exactly what they enqueue without this section.  The per-kernel entry points and the slab calls never sample.
+ * sph_stats_sample takes ONE sample of the current state outside a step, with the same two launches, at the current simulated time;
+ * it does not touch steps_seen.
+ * ONE SAMPLE: (a) the grid scatter of "Field sampling" -- its kernel, its pair term, its selection, its i64 terms -- with the fields
+ * vx vy vz and no gradients, into a scratch of the statistics' own: per node count, weight, S_x, S_y, S_z.  The planes of the last
+ * sph_sample_grid are NOT touched: they, and a mesh cut from them, survive a run with statistics.  (b) the FOLD, per node:
+ *     wet  <=>  weight >= wet_min && weight > 0
+ *     a node that is not wet adds nothing (no division is evaluated for it); a wet node, in f64, nothing contracted:
+ *     u_a = (double)S_a / (double)weight        a = x, y, z; i64 -> f64 correctly rounded, the IEEE division
+ *     u_a = fmin(fmax(u_a, -1024.0), 1024.0)
+ *     n_wet      += 1
+ *     sum_w      += weight                                    (exact)
+ *     sum_u[a]   += llrint(u_a * 2^32)
+ *     sum_uu[ab] += llrint((u_a * u_b) * 2^24)                ab = xx xy xz yy yz zz; the product rounds once, the scalings are exact
+ * and the node's five scratch words are zeroed for the next sample.  All accumulators are i64 planes over the nodes, node (k0, k1, k2)
+ * at (k0 * n[1] + k1) * n[2] + k2.  wet_min is in the units of the sampler's weight plane: llrint(fill * 2^30).
+ * BOUND: a first-moment term is at most 2^42 and a second-moment term at most 2^44 in magnitude (equality only at the clamp), so
+ * 2^19 samples fit an i64: capacity <= SPH_STATS_MAX_SAMPLES.  Once samples == capacity further samples are SKIPPED -- no launch --
+ * and counted in `dropped`, as the tracers count dropped frames.
+ * DETERMINISTIC: the scatter's sums are integers, every node of the fold has one owner and the fold has no atomics; there is no float
+ * or double atomic anywhere.  The result is one function of the sampled states.
+ * WHAT IS WRITTEN: the statistics' own planes, nothing else.  Density / pressure of a fused step are not materialised, no
+ * derived-state flag is touched (SPH_OPT_SORT_FAST and SPH_OPT_SORT_LEAN stay eligible): a run with statistics ends bit-identical
+ * to the run without.
+ * sph_stats_set REPLACES the set and zeroes its accumulators and counters; NULL clears the set (and frees nothing); it synchronises.
+ * sph_stats_reset zeroes accumulators and counters (steps_seen too) and keeps the set; it synchronises.  sph_stats_info returns host
+ * data only and does not synchronise: the grid, `every`, the samples taken and dropped, steps_seen and the simulated times of the
+ * first and the last sample (0 while there is none); all zero without a set.  sph_stats_download copies n_wet [nodes], sum_w
+ * [nodes], sum_u [3][nodes], sum_uu [6][nodes] (any pointer may be NULL) and synchronises.  The planes are allocated by the first
+ * set, again when a later grid needs more, and freed with the context; a context that never registers statistics allocates nothing.
+ * SPH_E_INVALID: every refusal of sph_sample_grid for the grid (the same checks); grid.fields other than 0 or vx | vy | vz;
+ * every < 1; capacity outside [1, SPH_STATS_MAX_SAMPLES]; wet_min < 0; a download whose `nodes` does not match the set.
+ * SPH_E_STATE: a sample, download or reset without a registered set; a slab rank (set, sample, download, reset).  A refused
+ * sph_stats_set changes nothing: the last good set goes on being sampled and stays downloadable.  Statistics are not part of a
+ * checkpoint.  csrc/sph_stats.hip describes the fold kernel.
+ * ==================================================================================== */
+#define SPH_STATS_MAX_SAMPLES (1 << 19)
+typedef struct SphStatsParams {
+    SphSampleGrid grid;             /* geometry, inv_h and selection as for sph_sample_grid; fields 0 or vx | vy | vz */
+    int32_t every;                  /* >= 1: every every-th step of the context is sampled */
+    int32_t capacity;               /* samples the set accepts, in [1, SPH_STATS_MAX_SAMPLES] */
+    int64_t wet_min;                /* a node is wet iff weight >= wet_min && weight > 0; >= 0 */
+} SphStatsParams;
+typedef struct SphStatsInfo {
+    int64_t nodes;                  /* of the registered grid (0: no set) */
+    int32_t n[3];
+    int32_t every;
+    int64_t samples, dropped, steps_seen;
+    double t_first, t_last;         /* simulated time of the first and the last sample taken */
+} SphStatsInfo;
+int32_t sph_stats_set(SphContext* ctx, const SphStatsParams* params);   /* NULL clears; synchronises */
+int32_t sph_stats_sample(SphContext* ctx);                              /* one sample of the current state; enqueues */
+int32_t sph_stats_info(SphContext* ctx, SphStatsInfo* info);            /* host data only */
+int32_t sph_stats_download(SphContext* ctx, int64_t* n_wet, int64_t* sum_w, int64_t* sum_u /*[3][nodes]*/, int64_t* sum_uu /*[6][nodes]*/,
+                           int64_t nodes);                              /* any pointer may be NULL; synchronises */
+int32_t sph_stats_reset(SphContext* ctx);                               /* keeps the set; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,20 @@ class SphTracerInfo(C.Structure):
     _fields_ = [("m", C.c_int32), ("reserved_", C.c_int32), ("advances", C.c_int64), ("frames", C.c_int64), ("dropped", C.c_int64)]
 
 
+STATS_MAX_SAMPLES = 1 << 19
+
+
+class SphStatsParams(C.Structure):
+    """Mirror of `struct SphStatsParams` (include/sph_hip.h)."""
+    _fields_ = [("grid", SphSampleGrid), ("every", C.c_int32), ("capacity", C.c_int32), ("wet_min", C.c_int64)]
+
+
+class SphStatsInfo(C.Structure):
+    """Mirror of `struct SphStatsInfo` (include/sph_hip.h)."""
+    _fields_ = [("nodes", C.c_int64), ("n", C.c_int32 * 3), ("every", C.c_int32), ("samples", C.c_int64), ("dropped", C.c_int64),
+                ("steps_seen", C.c_int64), ("t_first", C.c_double), ("t_last", C.c_double)]
+
+
 TRACERS_MAX = 1 << 22
 
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
@@ -317,6 +331,11 @@ SYMBOLS = [
     ("sph_tracers_info", C.c_int32, [_ctx, C.POINTER(SphTracerInfo)]),
     ("sph_tracers_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     ("sph_tracers_history_download", C.c_int32, [_ctx, C.c_void_p, C.c_int64, C.c_int32]),
+    ("sph_stats_set", C.c_int32, [_ctx, C.POINTER(SphStatsParams)]),
+    ("sph_stats_sample", C.c_int32, [_ctx]),
+    ("sph_stats_info", C.c_int32, [_ctx, C.POINTER(SphStatsInfo)]),
+    ("sph_stats_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    ("sph_stats_reset", C.c_int32, [_ctx]),
 ]
 
 _LIB = None

@@ -434,6 +434,7 @@ int32_t sph_destroy(SphContext* c) {
     sph_sample_release(c);
     sph_mesh_release(c);
     sph_tracers_release(c);
+    sph_stats_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
@@ -927,7 +928,7 @@ typedef int (*StepBody)(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_id
 // gather_dispatch).  The in-step consumers of aux between two sorts are the
 // kinematic poses (the id of a registered object's particles) and the rigid solve (ids and densities of dynamic solids): both
 // need solids, which the pure-fluid rule of the lean scatter excludes, and registered motions are excluded here by name.  The
-// tracers read xm / vf and the cell array only.
+// tracers read xm / vf and the cell array only, the running statistics xm / vf only.
 static bool step_aux_dead(const SphContext* c, StepBody body) {
     return body == step_sweeps && c->opt_fused && c->opt_gather_impl == 1 && sphk_brick_sweeps_reach(c) && c->n_kin == 0;
 }
@@ -954,6 +955,10 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         if (ev) SPH_HIP(c, hipEventRecord(ev[1], c->stream));
         if (c->tracers) {   // a registered tracer set advances with v(t_k) through the cell array of this sort (sph_hip.h, "Passive tracers")
             rc = sph_tracers_advance(c);
+            if (rc) return rc;
+        }
+        if (c->stats_set) {   // a registered statistics set samples x(t_k), v(t_k) every `every`-th step (sph_hip.h, "Running flow statistics")
+            rc = sph_stats_step(c);
             if (rc) return rc;
         }
         rc = body(c, ev, dynamic_ids, n_dynamic, it + 1 == n_steps);

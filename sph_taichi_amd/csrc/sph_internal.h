@@ -103,6 +103,7 @@ struct SphSurface;  // surface frames (sph_surface.hip): the style and the per-p
 struct SphSample;   // field sampling (sph_sample.hip): the grid's and the points' planes; null until sph_sample_grid / sph_sample_points
 struct SphMesh;     // mesh extraction (sph_mesh.hip): the classification, the cell -> vertex map and the mesh's buffers; null until sph_mesh_extract
 struct SphTracers;  // passive tracers (sph_tracers.hip): the set's buffers, parameters and counters; null until sph_tracers_set
+struct SphStatsSet; // running flow statistics (sph_stats.hip): the registered grid, its scratch and accumulator planes, the counters; null until sph_stats_set
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -220,6 +221,7 @@ struct SphContext {
     SphSample* sample;
     SphMesh* mesh;
     SphTracers* tracers;
+    SphStatsSet* stats_set;
     // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
     double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
@@ -319,6 +321,8 @@ void sph_sample_release(SphContext* c);  // sph_sample.hip: frees the sampled pl
 void sph_mesh_release(SphContext* c);    // sph_mesh.hip: frees the extraction's scratch and the mesh's buffers (sph_destroy)
 void sph_tracers_release(SphContext* c); // sph_tracers.hip: frees the tracer buffers and the history (sph_destroy)
 int sph_tracers_advance(SphContext* c);   // sph_tracers.hip: the step loops' hook behind the sort: one launch, or nothing when no set is registered
+void sph_stats_release(SphContext* c);   // sph_stats.hip: frees the statistics planes (sph_destroy)
+int sph_stats_step(SphContext* c);        // sph_stats.hip: the step loops' hook behind the sort: counts the step; two launches when a sample is due
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -71,20 +71,7 @@ struct SphSample {
     float pts_host[3 * SPH_SAMPLE_MAX_POINTS];
 };
 
-struct SampleCommon {
-    float inv_h, k_w;
-    int fields;               // mask
-    int channels;             // 2 + popcount(fields)
-    SphSel sel;
-};
-
-struct SampleGridDev {
-    int n[3];
-    float origin[3], spacing[3], inv_spacing[3];
-    float h;                  // the radius the footprints are built with: 1 / inv_h
-    long long nodes;
-    long long* planes;
-};
+// (SampleCommon and SampleGridDev, the kernels' arguments: sph_sample_grid.h)
 
 struct NodeBox { int lo[3], hi[3]; };   // inclusive; empty when lo > hi on any axis
 
@@ -356,16 +343,9 @@ static int sample_clear(SphContext* c, long long* p, size_t words) {
     return 0;
 }
 
-// sph_sample_grid (with_grad false: `gradients` is not read) and sph_sample_grid_gradients
-static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad, int32_t gradients, const char* who) {
-    if (c && !p) return sample_fail(c, SPH_E_INVALID, who, "the grid is NULL");
-    if (int rc = sph_observe_enter(c, who, " (its ghost records would be counted twice); fields are sampled on single-domain contexts only")) return rc;
-    SampleCommon q;
-    if (int rc = sample_common(c, who, p->fields, &p->select, p->inv_h, &q)) return rc;
-    const int n_fields = q.channels - 2;
-    if (with_grad)
-        if (int rc = sample_gradients(c, who, gradients, &q)) return rc;
-    SampleGridDev g;
+// the geometry of a public grid, checked: fills all of *g but its planes
+static int sample_grid_geometry(SphContext* c, const char* who, const SphSampleGrid* p, SampleGridDev* out) {
+    SampleGridDev& g = *out;
     g.h = 1.0f / p->inv_h;
     if (!std::isfinite(g.h)) return sample_fail(c, SPH_E_INVALID, who, "inv_h must be finite and positive (its reciprocal is not finite)");
     long long nodes = 1;
@@ -386,6 +366,37 @@ static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad
         }
         g.n[a] = p->n[a]; g.origin[a] = p->origin[a]; g.spacing[a] = p->spacing[a]; g.inv_spacing[a] = 1.0f / p->spacing[a];
     }
+    g.nodes = nodes;
+    g.planes = nullptr;
+    return 0;
+}
+
+int sph_sample_grid_spec(SphContext* c, const char* who, const SphSampleGrid* p, SampleCommon* q, SampleGridDev* g) {
+    if (int rc = sample_common(c, who, p->fields, &p->select, p->inv_h, q)) return rc;
+    return sample_grid_geometry(c, who, p, g);
+}
+
+int sph_sample_grid_scatter(SphContext* c, const SampleCommon& q, const SampleGridDev& g) {
+    const SphLive in = sph_live(c);
+    if (in.N <= 0) return 0;
+    const SphWalk w = sph_observe_walk(in.N, STPB, SG_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_sample_grid, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g);
+    SPH_LAUNCH_CHECK(c);
+    return 0;
+}
+
+// sph_sample_grid (with_grad false: `gradients` is not read) and sph_sample_grid_gradients
+static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad, int32_t gradients, const char* who) {
+    if (c && !p) return sample_fail(c, SPH_E_INVALID, who, "the grid is NULL");
+    if (int rc = sph_observe_enter(c, who, " (its ghost records would be counted twice); fields are sampled on single-domain contexts only")) return rc;
+    SampleCommon q;
+    if (int rc = sample_common(c, who, p->fields, &p->select, p->inv_h, &q)) return rc;
+    const int n_fields = q.channels - 2;
+    if (with_grad)
+        if (int rc = sample_gradients(c, who, gradients, &q)) return rc;
+    SampleGridDev g;
+    if (int rc = sample_grid_geometry(c, who, p, &g)) return rc;
+    const long long nodes = g.nodes;
     if (int rc = sample_state(c, who)) return rc;
     SphSample* s = c->sample;
     const size_t words = (size_t)q.channels * (size_t)nodes;
@@ -396,18 +407,18 @@ static int sample_grid_run(SphContext* c, const SphSampleGrid* p, bool with_grad
     }
     if (p->fields & (SPH_SAMPLE_DENSITY | SPH_SAMPLE_PRESSURE))
         if (int rc = sph_ensure_aux(c)) return rc;   // density / pressure of a fused step live in eos2 until somebody asks
-    g.nodes = nodes;
     g.planes = s->grid;
     if (int rc = sample_clear(c, s->grid, words)) return rc;
     if (int rc = sph_ensure_pid(c)) return rc;   // the kernels below read aux
-    const SphLive in = sph_live(c);
-    if (in.N > 0) {
-        const SphWalk w = sph_observe_walk(in.N, STPB, SG_MAX_BLOCKS);
-        if (with_grad)
+    if (with_grad) {
+        const SphLive in = sph_live(c);
+        if (in.N > 0) {
+            const SphWalk w = sph_observe_walk(in.N, STPB, SG_MAX_BLOCKS);
             hipLaunchKernelGGL(k_sample_grid_grad, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g, (int)gradients);
-        else
-            hipLaunchKernelGGL(k_sample_grid, dim3(w.blocks), dim3(STPB), 0, c->stream, in.xm, in.vf, in.aux, in.N, w.per_block, q, g);
-        SPH_LAUNCH_CHECK(c);
+            SPH_LAUNCH_CHECK(c);
+        }
+    } else if (int rc = sph_sample_grid_scatter(c, q, g)) {
+        return rc;
     }
     s->grid_nodes = nodes;
     for (int a = 0; a < 3; ++a) { s->grid_n[a] = g.n[a]; s->grid_origin[a] = g.origin[a]; s->grid_spacing[a] = g.spacing[a]; }

@@ -115,6 +115,7 @@ class ParticleSystem:
         if self._motions and slab is not None:
             raise NotImplementedError("kinematic bodies (\"motion\" in the scene file) exist on single-domain contexts only")
         self.tracers = None      # the registered tracer set (tracers.Tracers): None until set_tracers
+        self.statistics = None   # the registered statistics set (stats.Statistics): None until set_statistics
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -487,6 +488,26 @@ class ParticleSystem:
         """Remove the tracer set: the steps enqueue what they did before any was set.  `self.tracers` becomes an empty set."""
         from . import tracers as _tracers
         self.tracers = _tracers.clear_tracers(self)
+
+    def set_statistics(self, origin=None, spacing=None, shape=None, objects=None, material="fluid", every=10, capacity=None, wet=0.4):
+        """Register running flow statistics on a grid (`origin`, `spacing`, `shape`, `objects`, `material` exactly as for
+        `sample_grid`; a slice is a shape with a 1 in it): from now on every `every`-th step of the device loop (`solver.step(n)`)
+        samples the Shepard-mean velocity of the selected particles at the nodes and folds it into integer accumulators on the
+        device; a node counts as wet in a sample when its Shepard sum reaches `wet`.  `capacity` bounds the number of samples
+        (default and maximum 2^19).  A whole-domain volume costs many steps' worth of time per sample -- `every` is what makes it
+        affordable -- while a slice can run every step ("Running flow statistics").  Replaces the set; returns
+        `self.statistics` (stats.Statistics): mean_velocity(), reynolds_stress(), rms_velocity(), tke(), intermittency(),
+        mean_fill(), accumulators(), write_vtk(path), reset().  Statistics are not part of `save_state`."""
+        from . import stats as _stats
+        self.statistics = _stats.set_statistics(self, spacing=spacing, origin=origin, shape=shape, objects=objects, material=material,
+                                                every=every, capacity=capacity, wet=wet)
+        return self.statistics
+
+    def clear_statistics(self):
+        """Remove the statistics set: the steps enqueue what they did before any was set.  `self.statistics` becomes None."""
+        from . import stats as _stats
+        _stats.clear_statistics(self)
+        self.statistics = None
 
     def _step_call(self, name, n_steps, ids, n_ids, dt):
         """sph_step / sph_dfsph_step; with tracers registered, the times of the history frames the call stored are noted."""

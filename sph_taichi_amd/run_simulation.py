@@ -46,6 +46,11 @@ A Configuration with "tracers": {"points": [[x, y, z], ...]} or {"lattice": {"st
 "recordEvery" (default 1), "minFill" (default 0.2) and "objects", registers passive tracers after initialize() (tracers.py): they
 are advected on the device inside every step, and `{scene}_output/tracers_{cnt:06}.vtk` per exported interval holds the pathlines
 so far (legacy ASCII POLYDATA, one polyline per tracer, point data `time`); `--tracers out.vtk` writes the final pathlines.
+A Configuration with "statistics": {"spacing": s, "origin": [..], "shape": [..], "objects": [0], "every": 10, "capacity": n,
+"wet": 0.4} (every key optional) registers running flow statistics after initialize() (stats.py): every `every`-th step is sampled
+on the device inside the step, and `{scene}_output/statistics.vtk` at the end of the run holds intermittency, mean fill, mean and
+RMS velocity, turbulent kinetic energy and the Reynolds stresses on that grid (a legacy binary STRUCTURED_POINTS volume);
+`--statistics out.vtk` writes the same file there as well.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -90,6 +95,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "from the fluid (count, fill, the fields)")
     ap.add_argument("--tracers", default="", metavar="PATH",
                     help="write the pathlines of the scene's \"tracers\" here after the last frame (legacy ASCII VTK polylines)")
+    ap.add_argument("--statistics", default="", metavar="PATH",
+                    help="write the running flow statistics of the scene's \"statistics\" grid here after the last frame (legacy binary VTK volume)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
                     help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
@@ -132,7 +139,12 @@ def main(argv=None):
     tracers_spec = _tracers.tracers_config(config)     # "tracers": None when the key is absent
     if args.tracers and tracers_spec is None:
         raise ValueError('--tracers needs a "tracers" object in the scene\'s Configuration')
-    if output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None:
+    from . import stats as _stats
+    stats_spec = _stats.statistics_config(config)      # "statistics": None when the key is absent
+    if args.statistics and stats_spec is None:
+        raise ValueError('--statistics needs a "statistics" object in the scene\'s Configuration')
+    if (output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None
+            or stats_spec is not None):
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -164,6 +176,8 @@ def main(argv=None):
         ps.set_tracers(tracers_spec["points"], min_fill=tracers_spec["min_fill"], record_every=tracers_spec["record_every"],
                        record_capacity=_tracers.history_capacity(m, args.frames * substeps, tracers_spec["record_every"]),
                        objects=tracers_spec["objects"])
+    if stats_spec is not None:
+        ps.set_statistics(**stats_spec)
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
     probes_out = open(args.probes, "w") if probes_spec is not None else None
@@ -273,6 +287,13 @@ def main(argv=None):
         report["tracers"] = {"m": info.m, "advances": info.advances, "frames": info.frames, "dropped": info.dropped}
         if args.tracers:
             ps.tracers.write_vtk(args.tracers)
+    if stats_spec is not None:
+        info = ps.statistics.info()
+        report["statistics"] = {"shape": list(info.shape), "every": info.every, "samples": info.samples, "dropped": info.dropped,
+                                "steps_seen": info.steps_seen, "t_first": info.t_first, "t_last": info.t_last}
+        ps.statistics.write_vtk(f"{scene_name}_output/statistics.vtk")
+        if args.statistics:
+            ps.statistics.write_vtk(args.statistics)
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
