@@ -1075,6 +1075,82 @@ int32_t sph_stats_download(SphContext* ctx, int64_t* n_wet, int64_t* sum_w, int6
                            int64_t nodes);                              /* any pointer may be NULL; synchronises */
 int32_t sph_stats_reset(SphContext* ctx);                               /* keeps the set; synchronises */
 
+/* ======================================================================================
+ * Fluid loads (the reference has none; the force sweep keeps the boundary term only as the fluid's acceleration): a context may hold
+ * ONE registered load set -- up to SPH_LOADS_MAX_OBJECTS solid objects (static, kinematic or dynamic) -- for which it records, as a
+ * time series ON THE DEVICE, the force and the torque the fluid exerts on each object.  WCSPH only.
+ * THE QUANTITY.  For a solid particle j of a selected object and a fluid particle i with r = |x_i - x_j| < h:
+ *     F_j = sum_i  m_i * rho0 * m_V_j * (p_i / rho_i^2 + p_i / rho0^2) * gradW(x_i - x_j)
+ * which is minus m_i times the acceleration WCSPH.py:58-68 gives fluid i from boundary particle j (the reference has no boundary
+ * viscosity, so this is the whole fluid-solid interaction).  Per object: force = sum_j F_j; torque = sum_j (x_j - c) x F_j about ONE
+ * fixed world point c of the set (`about`); the number of contributing pairs; of wet solid particles (at least one pair); of
+ * saturated terms.  Nine i64 per object and sample, in this order: Fx Fy Fz Tx Ty Tz pairs wet saturated.  Forces are in N and
+ * torques in N m at scale 2^24: value = integer / 2^24.
+ * TERM BY TERM.  Candidates of target j are the records of the 27 cells around the cell the sort hashed j into (its clamped cell
+ * coordinates), read through the cell array; a candidate contributes iff it is of fluid material and, with the pair geometry of
+ * "Field sampling" taken verbatim (f32: d_a = x_i,a - x_j,a; r2 = (dx*dx + dy*dy) + dz*dz; r = sqrtf(r2) correctly rounded;
+ * q = r * inv_h, inv_h = 1.f / support_radius), q <= 1.0f and r > 1e-5f.  (A pair that a rounding error puts outside the 27 cells
+ * although its q <= 1.0f does not contribute; its term would be of the order of the last bit of q.)  Then in f64, every operation
+ * an IEEE multiply, divide or subtract, nothing contracted, no f32 divide, no reciprocal or reciprocal square root:
+ *     g    = q <= 0.5 ? q * (3.0 * q - 2.0) : -((1.0 - q) * (1.0 - q))
+ *     dp   = p_i / (rho_i * rho_i) + p_i / (rho0 * rho0)
+ *     coef = (((m_i * rho0) * m_V_j) * dp) * ((k_dw * g) / (r * h))
+ *     f_a  = coef * d_a;   c_a = fmin(fmax(f_a, -65536.0), 65536.0);   saturated += (c_a != f_a);   F_j,a += llrint(c_a * 2^24)
+ * with m_i, rho_i, p_i the f32 mass, density and pressure of i as this step computed them, m_V_j the f32 boundary volume, and rho0,
+ * k_dw, h = support_radius the context's f32 parameters, each converted to f64.  A NaN ends at -65536 and is counted.  F_j is the
+ * INTEGER sum of its pair terms.  The torque term of target j, with a_b = (double)(x_j,b - about_b) (the subtraction in f32) and
+ * F_b = (double)F_j,b / 2^24:
+ *     T_x = a_y * F_z - a_z * F_y  (cyclic);   s = T_a * 2^24;   c = fmin(fmax(s, -2^40), 2^40);   saturated += (c != s);   T += llrint(c)
+ * OVERFLOW BUDGET: a force term is at most 2^40 in magnitude and so is a torque term: 2^22 pair terms (or targets) AT THE CLAMP
+ * still fit an i64.  DETERMINISTIC: every accumulation is an integer add (lane sums, DPP row sums, no-return i64 atomics into the
+ * sample's own row), so the nine numbers are one function of the sampled state, whatever the lane split, the launch order or the
+ * order the atomics arrive in.  There is no float or double atomic.
+ * THE HOOK: while a set is registered, every step of sph_step (and of sph_sweeps) is counted (steps_seen, from 0 at registration), and
+ * step k is SAMPLED iff steps_seen % every == 0 before it is counted.  The sample is enqueued directly behind the step's density and
+ * equation of state and before its force sweep: the positions are x(t_k), the cell array is this step's sort, p and rho are this
+ * step's -- exactly what the force sweep then uses.  Density and pressure of a fused step are materialised in the particle record
+ * first (the values every later reader would get anyway).  Sample k writes row k of the history at time = the simulated time t_k.  One
+ * 4-byte clear and two launches per sampled step on the context's stream, no synchronisation, nothing crosses to the host.  Once
+ * samples == capacity further samples are SKIPPED -- no launch -- and counted in `dropped`.  With no set registered (never set, or
+ * cleared) the step enqueues exactly what it enqueues without this section.  While a set is registered SPH_OPT_SORT_LEAN is not
+ * taken (the sample reads the particle record); positions and velocities of a run with a set are bit-identical to the run without.
+ * sph_dfsph_step with a registered set returns SPH_E_STATE: DFSPH couples through velocity changes, loads there are out of scope.
+ * sph_loads_sample takes ONE sample of the current state outside a step -- for callers that drive the kernels stage by stage -- with
+ * whatever density and pressure the particle record holds; it needs the neighbour structure of the current positions
+ * (sph_initialize_particle_system) and does not touch steps_seen.
+ * sph_loads_set REPLACES the set, zeroes its history and counters and synchronises; NULL clears the set (and frees nothing).
+ * sph_loads_reset zeroes history and counters and keeps the set; it synchronises.  sph_loads_info returns host data only.
+ * sph_loads_download copies rows [samples][n_objects][9] and times [samples] (either may be NULL), `samples` and `n_objects` being
+ * exactly the info's, synchronises, then checks the device's error flags.  Buffers are allocated by the first set (a target list of
+ * the context's record capacity, the history, the times), grow only and are freed with the context.
+ * SPH_E_INVALID: n_objects outside [1, SPH_LOADS_MAX_OBJECTS]; an object id outside [0, the context's n_objects); a duplicate id; a
+ * non-finite `about`; every < 1; capacity < 1 or a history above 2^31 bytes; a download whose sizes do not match.
+ * SPH_E_STATE: a sample, download or reset without a registered set; a sample without the neighbour structure; sph_dfsph_step with a
+ * registered set; a slab rank (every entry but info).  A refused sph_loads_set changes nothing.  Loads are not part of a checkpoint
+ * (save_state).  csrc/sph_loads.hip describes the kernels.
+ * ==================================================================================== */
+#define SPH_LOADS_MAX_OBJECTS 32
+#define SPH_LOADS_ROW_WORDS 9
+#define SPH_LOADS_SCALE_LOG2 24
+typedef struct SphLoadParams {
+    int32_t object_ids[SPH_LOADS_MAX_OBJECTS];   /* slot k of every history row is object_ids[k] */
+    int32_t n_objects;              /* in [1, SPH_LOADS_MAX_OBJECTS] */
+    float about[3];                 /* the fixed world point the torques are about */
+    int32_t every;                  /* >= 1: every every-th step of the context is sampled */
+    int32_t capacity;               /* >= 1: rows the history holds */
+} SphLoadParams;
+typedef struct SphLoadInfo {
+    int32_t n_objects;              /* of the registered set (0: no set) */
+    int32_t every;
+    int64_t samples, dropped, steps_seen;
+} SphLoadInfo;
+int32_t sph_loads_set(SphContext* ctx, const SphLoadParams* params);    /* NULL clears; synchronises */
+int32_t sph_loads_sample(SphContext* ctx);                              /* one sample of the current state; enqueues */
+int32_t sph_loads_info(SphContext* ctx, SphLoadInfo* info);             /* host data only */
+int32_t sph_loads_download(SphContext* ctx, int64_t* rows /*[samples][n_objects][9]*/, double* times /*[samples]*/, int64_t samples,
+                           int32_t n_objects);                          /* either pointer may be NULL; synchronises */
+int32_t sph_loads_reset(SphContext* ctx);                               /* keeps the set; synchronises */
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,20 @@ class SphStatsInfo(C.Structure):
                 ("steps_seen", C.c_int64), ("t_first", C.c_double), ("t_last", C.c_double)]
 
 
+LOADS_MAX_OBJECTS, LOADS_ROW_WORDS, LOADS_SCALE_LOG2 = 32, 9, 24
+
+
+class SphLoadParams(C.Structure):
+    """Mirror of `struct SphLoadParams` (include/sph_hip.h)."""
+    _fields_ = [("object_ids", C.c_int32 * LOADS_MAX_OBJECTS), ("n_objects", C.c_int32), ("about", _F3), ("every", C.c_int32),
+                ("capacity", C.c_int32)]
+
+
+class SphLoadInfo(C.Structure):
+    """Mirror of `struct SphLoadInfo` (include/sph_hip.h)."""
+    _fields_ = [("n_objects", C.c_int32), ("every", C.c_int32), ("samples", C.c_int64), ("dropped", C.c_int64), ("steps_seen", C.c_int64)]
+
+
 TRACERS_MAX = 1 << 22
 
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
@@ -336,6 +350,11 @@ SYMBOLS = [
     ("sph_stats_info", C.c_int32, [_ctx, C.POINTER(SphStatsInfo)]),
     ("sph_stats_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     ("sph_stats_reset", C.c_int32, [_ctx]),
+    ("sph_loads_set", C.c_int32, [_ctx, C.POINTER(SphLoadParams)]),
+    ("sph_loads_sample", C.c_int32, [_ctx]),
+    ("sph_loads_info", C.c_int32, [_ctx, C.POINTER(SphLoadInfo)]),
+    ("sph_loads_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    ("sph_loads_reset", C.c_int32, [_ctx]),
 ]
 
 _LIB = None

@@ -104,6 +104,7 @@ struct SphSample;   // field sampling (sph_sample.hip): the grid's and the point
 struct SphMesh;     // mesh extraction (sph_mesh.hip): the classification, the cell -> vertex map and the mesh's buffers; null until sph_mesh_extract
 struct SphTracers;  // passive tracers (sph_tracers.hip): the set's buffers, parameters and counters; null until sph_tracers_set
 struct SphStatsSet; // running flow statistics (sph_stats.hip): the registered grid, its scratch and accumulator planes, the counters; null until sph_stats_set
+struct SphLoadSet;  // fluid loads on solid objects (sph_loads.hip): the target list, the history, the set and the counters; null until sph_loads_set
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -222,6 +223,7 @@ struct SphContext {
     SphMesh* mesh;
     SphTracers* tracers;
     SphStatsSet* stats_set;
+    SphLoadSet* loads;
     // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
     double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
@@ -323,6 +325,9 @@ void sph_tracers_release(SphContext* c); // sph_tracers.hip: frees the tracer bu
 int sph_tracers_advance(SphContext* c);   // sph_tracers.hip: the step loops' hook behind the sort: one launch, or nothing when no set is registered
 void sph_stats_release(SphContext* c);   // sph_stats.hip: frees the statistics planes (sph_destroy)
 int sph_stats_step(SphContext* c);        // sph_stats.hip: the step loops' hook behind the sort: counts the step; two launches when a sample is due
+void sph_loads_release(SphContext* c);   // sph_loads.hip: frees the load set's list and history (sph_destroy)
+bool sph_loads_armed(const SphContext* c);  // sph_loads.hip: a load set is registered (its samples read aux inside the step)
+int sph_loads_step(SphContext* c);        // sph_loads.hip: step_sweeps' hook behind density and EOS: counts the step; two launches when a sample is due
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -1,6 +1,6 @@
 // sph_observe.h -- what the read-only observers of the particle state share (sph_diag.hip, sph_columns.hip, sph_export.hip,
-// sph_render.hip, sph_surface.hip, sph_sample.hip, sph_mesh.hip, sph_tracers.hip): the view of the live records, the entry
-// checks, the allocation and download sequences, the grid of a contiguous walk, the 64-bit shuffles and THE particle selection
+// sph_render.hip, sph_surface.hip, sph_sample.hip, sph_mesh.hip, sph_tracers.hip, sph_stats.hip, sph_loads.hip): the view of the live records, the entry
+// checks, the allocation and download sequences, the grid of a contiguous walk, the 64-bit shuffles, the DPP row sums and THE particle selection
 // (SphSel: who is selected by a material and a list of object ids -- the export, the field colouring of both frame styles, the
 // field range, the samplers with the mesh cut from their grid, and the tracers all ask sph_selected).  An observer reads the
 // records behind whatever the stream holds, writes buffers of its own and no particle state.
@@ -117,5 +117,32 @@ __device__ __forceinline__ long long shfl_xor_i64(long long v, int m) {
 __device__ __forceinline__ long long shfl_up_i64(long long v, int off) {
     const int lo = __shfl_up((int)(v & 0xffffffffll), off, 64), hi = __shfl_up((int)(v >> 32), off, 64);
     return ((long long)hi << 32) | (unsigned)lo;
+}
+
+// ---- one DPP row (16 lanes of a wave64) as a unit: the tracer gather and the load gather give a row to each target ----
+template <int CTRL>
+__device__ __forceinline__ int row_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
+
+template <int CTRL>
+__device__ __forceinline__ long long row_dpp_i64(long long v) {
+    const int lo = row_dpp<CTRL>((int)(v & 0xffffffffll)), hi = row_dpp<CTRL>((int)(v >> 32));
+    return ((long long)hi << 32) | (unsigned)lo;
+}
+
+// the sum over the 16 lanes of a DPP row, in every lane of it (row_ror:8, :4, :2, :1 = dpp_ctrl 0x120 + n); all lanes of the wave active
+__device__ __forceinline__ long long row_sum(long long v) {
+    v += row_dpp_i64<0x128>(v);
+    v += row_dpp_i64<0x124>(v);
+    v += row_dpp_i64<0x122>(v);
+    v += row_dpp_i64<0x121>(v);
+    return v;
+}
+
+__device__ __forceinline__ int row_sum(int v) {
+    v += row_dpp<0x128>(v);
+    v += row_dpp<0x124>(v);
+    v += row_dpp<0x122>(v);
+    v += row_dpp<0x121>(v);
+    return v;
 }
 #endif  // __HIPCC__

@@ -64,32 +64,6 @@ struct TracerArgs {
     SphSel sel;
 };
 
-template <int CTRL>
-__device__ __forceinline__ int row_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-
-template <int CTRL>
-__device__ __forceinline__ long long row_dpp_i64(long long v) {
-    const int lo = row_dpp<CTRL>((int)(v & 0xffffffffll)), hi = row_dpp<CTRL>((int)(v >> 32));
-    return ((long long)hi << 32) | (unsigned)lo;
-}
-
-// the sum over the 16 lanes of a DPP row, in every lane of it (row_ror:8, :4, :2, :1 = dpp_ctrl 0x120 + n); all lanes of the wave active
-__device__ __forceinline__ long long row_sum(long long v) {
-    v += row_dpp_i64<0x128>(v);
-    v += row_dpp_i64<0x124>(v);
-    v += row_dpp_i64<0x122>(v);
-    v += row_dpp_i64<0x121>(v);
-    return v;
-}
-
-__device__ __forceinline__ int row_sum(int v) {
-    v += row_dpp<0x128>(v);
-    v += row_dpp<0x124>(v);
-    v += row_dpp<0x122>(v);
-    v += row_dpp<0x121>(v);
-    return v;
-}
-
 __global__ __launch_bounds__(TR_TPB) void k_tracers_advance(const float4* __restrict__ xm, const float4* __restrict__ vf,
                                                             const int* __restrict__ cell_end, TracerArgs a, TracerBufs b) {
     const int sub = threadIdx.x & (TR_ROW - 1);

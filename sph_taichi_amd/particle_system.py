@@ -116,6 +116,7 @@ class ParticleSystem:
             raise NotImplementedError("kinematic bodies (\"motion\" in the scene file) exist on single-domain contexts only")
         self.tracers = None      # the registered tracer set (tracers.Tracers): None until set_tracers
         self.statistics = None   # the registered statistics set (stats.Statistics): None until set_statistics
+        self.loads = None        # the registered load set (loads.Loads): None until set_loads
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -508,6 +509,24 @@ class ParticleSystem:
         from . import stats as _stats
         _stats.clear_statistics(self)
         self.statistics = None
+
+    def set_loads(self, objects=(1,), about=(0.0, 0.0, 0.0), every=1, capacity=4096):
+        """Register fluid loads on the solid `objects` (1 to 32 ids; static, kinematic or dynamic): from now on every `every`-th
+        WCSPH step of the device loop (`solver.step(n)`) samples, behind the step's density and pressure and before its force sweep,
+        the force and the torque about the world point `about` that the fluid exerts on each object -- the Akinci boundary term
+        of the force sweep, summed in integers on the device, so the series is one function of the run.  `capacity` bounds the
+        samples kept.  Replaces the set; returns `self.loads` (loads.Loads): force(), torque(about=None), pairs(), wet_particles(),
+        saturated(), times, impulse(), rows(), write_csv(path), sample(), reset().  A DFSPH step refuses to run with a set
+        registered.  Loads are not part of `save_state`."""
+        from . import loads as _loads
+        self.loads = _loads.set_loads(self, objects=objects, about=about, every=every, capacity=capacity)
+        return self.loads
+
+    def clear_loads(self):
+        """Remove the load set: the steps enqueue what they did before any was set.  `self.loads` becomes None."""
+        from . import loads as _loads
+        _loads.clear_loads(self)
+        self.loads = None
 
     def _step_call(self, name, n_steps, ids, n_ids, dt):
         """sph_step / sph_dfsph_step; with tracers registered, the times of the history frames the call stored are noted."""

@@ -51,6 +51,10 @@ A Configuration with "statistics": {"spacing": s, "origin": [..], "shape": [..],
 on the device inside the step, and `{scene}_output/statistics.vtk` at the end of the run holds intermittency, mean fill, mean and
 RMS velocity, turbulent kinetic energy and the Reynolds stresses on that grid (a legacy binary STRUCTURED_POINTS volume);
 `--statistics out.vtk` writes the same file there as well.
+A Configuration with "loads": {"objects": [1], "about": [x, y, z], "every": 1, "capacity": n} ("objects" required) registers fluid
+loads after initialize() (loads.py): every `every`-th step samples the force and torque of the fluid on each listed solid object on
+the device inside the step, and `{scene}_output/loads.csv` at the end of the run holds the series (one row per sample and object);
+`--loads out.csv` writes the same file there as well.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -97,6 +101,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write the pathlines of the scene's \"tracers\" here after the last frame (legacy ASCII VTK polylines)")
     ap.add_argument("--statistics", default="", metavar="PATH",
                     help="write the running flow statistics of the scene's \"statistics\" grid here after the last frame (legacy binary VTK volume)")
+    ap.add_argument("--loads", default="", metavar="PATH",
+                    help="write the force / torque series of the scene's \"loads\" objects here after the last frame (CSV)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
                     help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
@@ -143,8 +149,12 @@ def main(argv=None):
     stats_spec = _stats.statistics_config(config)      # "statistics": None when the key is absent
     if args.statistics and stats_spec is None:
         raise ValueError('--statistics needs a "statistics" object in the scene\'s Configuration')
+    from . import loads as _loads
+    loads_spec = _loads.loads_config(config)           # "loads": None when the key is absent
+    if args.loads and loads_spec is None:
+        raise ValueError('--loads needs a "loads" object in the scene\'s Configuration')
     if (output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None
-            or stats_spec is not None):
+            or stats_spec is not None or loads_spec is not None):
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -178,6 +188,8 @@ def main(argv=None):
                        objects=tracers_spec["objects"])
     if stats_spec is not None:
         ps.set_statistics(**stats_spec)
+    if loads_spec is not None:
+        ps.set_loads(**loads_spec)
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
     probes_out = open(args.probes, "w") if probes_spec is not None else None
@@ -294,6 +306,13 @@ def main(argv=None):
         ps.statistics.write_vtk(f"{scene_name}_output/statistics.vtk")
         if args.statistics:
             ps.statistics.write_vtk(args.statistics)
+    if loads_spec is not None:
+        info = ps.loads.info()
+        report["loads"] = {"objects": list(ps.loads.objects), "every": info.every, "samples": info.samples, "dropped": info.dropped,
+                           "steps_seen": info.steps_seen}
+        ps.loads.write_csv(f"{scene_name}_output/loads.csv")
+        if args.loads:
+            ps.loads.write_csv(args.loads)
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
