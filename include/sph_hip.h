@@ -1151,6 +1151,95 @@ int32_t sph_loads_download(SphContext* ctx, int64_t* rows /*[samples][n_objects]
                            int32_t n_objects);                          /* either pointer may be NULL; synchronises */
 int32_t sph_loads_reset(SphContext* ctx);                               /* keeps the set; synchronises */
 
+/* ======================================================================================
+ * Carried scalars (the reference has none: a particle carries position, velocity, density, pressure and an object colour): a context
+ * may hold ONE scalar set of K channels, 1 <= K <= SPH_SCALARS_MAX_CHANNELS -- dye, heat, a concentration -- that ride on the
+ * particles (advection is free in a Lagrangian method) and DIFFUSE between neighbours, on the device, inside the step.
+ * THE STORE.  int64 C[id][k], indexed by PERSISTENT id (channel fastest), the physical value times 2^32 (SPH_SCALARS_SCALE_LOG2),
+ * |value| <= 2^20 when set.  The sort never moves it and does not know it exists.  A difference of two stored values is an exact f64.
+ * WHO TAKES PART.  SOURCES: the records (fluid or solid) of up to SPH_SCALARS_MAX_SOURCES objects hold a prescribed value per channel
+ * (Dirichlet: a body at 350 K); a source is never updated and its stored value is not read.  CARRIERS: the records selected by
+ * `select` (as in "Field sampling") that are not of a source object and whose id is inside the store.  Every other record is
+ * invisible to the sum: zero flux, the natural SPH wall.
+ * ONE SAMPLE is one explicit Jacobi step of Brookshaw's Laplacian, the form of the reference's viscosity term (sph_base.py:71-78):
+ *     C_i <- C_i + a * sum_j m_V_j (C_j - C_i) * (-2 (r . gradW) / (r^2 + 0.01 h^2)),       a = dt * every * kappa
+ * TERM BY TERM.  All reads are from a SNAPSHOT of the participants' values taken before any write.  Candidates of carrier i are the
+ * records of the 27 cells around the cell the sort hashed i into (its clamped cell coordinates), read through the cell array, runs
+ * clipped to [0, N]; candidate j contributes iff it takes part and, with the pair geometry of "Field sampling" taken verbatim (f32:
+ * d = x_i - x_j; r2 = (dx*dx + dy*dy) + dz*dz; r = sqrtf(r2) correctly rounded; q = r * inv_h, inv_h = 1.f / support_radius),
+ * q <= 1.0f and r > 1e-5f (which excludes i itself).  Then in f64 from those f32 values, every operation an IEEE multiply, add or
+ * divide, nothing contracted (h = support_radius, k_dw the context's folded constant, both f32 converted):
+ *     g    = q <= 0.5 ? q * (3.0 * q - 2.0) : -((1.0 - q) * (1.0 - q))                        (as in "Fluid loads")
+ *     lap  = ((2.0 * (k_dw * g)) * r) / (h * (r * r + (0.01 * h) * h))                        <= 0
+ *     and per channel k, with a_k = ((double)dt * (double)every) * (double)kappa_k formed once per sample on the host:
+ *     w_k    = fmin(fmax((-(a_k * (double)m_V_j)) * lap, 0.0), 1.0)                            (a NaN gives 0)
+ *     term_k = llrint((double)(C_k[j] - C_k[i]) * w_k);      wsum_k += llrint(w_k * 2^32)
+ *     C_k[i] <- clamp(C_k[i] + sum_j term_k, -2^52, 2^52)
+ * A carrier whose wsum_k > 2^32 is counted in overshoot[k]: the explicit step is beyond its stability limit there (the new value
+ * may leave the range of its neighbours'), lower kappa or `every`.  A result the clamp changed is counted in saturated[k].  Both
+ * counters run from the set on.  BUDGET: |C_j - C_i| <= 2^53 and w <= 1, so 2^9 pair terms at the extreme still fit an i64.
+ * DETERMINISTIC: every sum is an integer sum (lane sums, DPP row sums), so the result depends neither on record order nor on the
+ * work split, and a brute-force model reproduces every word.  Where all participants have bit-equal m_V (one fluid),
+ * term_ij = -term_ji exactly, so with no sources sum_i C_k[i] is conserved to the last bit (unless a value saturates); with unequal
+ * volumes conservation holds to rounding only.
+ * THE HOOK: while a set is registered every step of sph_step and sph_dfsph_step is counted (steps_seen, from 0 at the set), and step k
+ * is SAMPLED iff steps_seen % every == 0 before it is counted; the sample is enqueued behind the step's sort and before its sweeps:
+ * positions x(t_k), this step's cell array.  One 4-byte clear and two launches on the context's stream (the stage: snapshot, roles
+ * and the carriers' index list with its count, which stays on the device; the diffusion), no synchronisation, nothing crosses to the
+ * host, no particle state is written: a run with a set is bit-identical in x, v, density, pressure to the run without, and keeps its
+ * lean and fast sorts.  With no set registered the step loops enqueue exactly what they enqueue without this section.  The
+ * per-kernel entries and the slab calls never sample.  sph_scalars_sample takes ONE sample of the current state outside a step; it
+ * needs the neighbour structure of the current positions (sph_initialize_particle_system) and does not touch steps_seen.
+ * sph_scalars_set REPLACES the set: `values` is f64 [n_ids][K] in id order (NULL: zeros), stored as llrint(value * 2^32); counters
+ * start from zero; params->K == 0 (or params NULL) clears the set (values and n_ids are then not read); synchronises.
+ * sph_scalars_info: host counters and the two device counters (synchronises).  sph_scalars_download: raw i64 [n_ids][K] and / or
+ * values f64 [n_ids][K] = raw / 2^32 (either may be NULL), n_ids being the set's; synchronises.
+ * sph_scalars_paint(ctx, channel, lo, hi, lut): one streaming pass that writes, for every carrier and source record, the table
+ * colour of its value (a source: the prescribed one) into the object colour of its id (SPH_F_COLOR, which both frame styles draw),
+ * and nothing else: s = (float)((double)C * 2^-32), then the index arithmetic of "Field colouring" verbatim -- t = (s - lo) * inv,
+ * inv = 1.f / (hi - lo); t = t >= 0 ? min(t, 1) : 0; idx = int(t * 255 + 0.5) -- and colour[c] = lut[idx][c], lut 256 x 3 int32
+ * in [0, 255].  An explicit call; other records keep their colour.  Enqueues.
+ * Buffers (store, snapshot, list, counters, table) are allocated by the first set, grow only and are freed with the context; a
+ * context that never sets scalars allocates nothing.
+ * TEST AID: the environment variable SPH_SCALARS_BLOCKS = b >= 1, read by sph_scalars_set, caps the diffusion's grid at b blocks of
+ * sixteen rows (it can only shrink the grid; results are the same words): the waves then take several trips over a short list, which
+ * a small test scene would never make them do.  Not for production use.
+ * SPH_E_INVALID: K outside [0, SPH_SCALARS_MAX_CHANNELS]; every < 1; n_sources outside [0, SPH_SCALARS_MAX_SOURCES]; a source object
+ * outside [0, the context's n_objects) or named twice; a selection out of range; kappa negative or not finite; a value (initial or
+ * source) not finite or beyond 2^20 in magnitude; n_ids < 1 or above the cold capacity; a download with another n_ids; paint: a
+ * channel outside [0, K), lo or hi not finite, lo >= hi, a reciprocal width that is not a positive finite f32, a NULL table or an
+ * entry outside [0, 255].  SPH_E_STATE: sample, download or paint without a set; a sample without the neighbour structure; a slab
+ * rank (every entry but info).  A refused call changes nothing: the last good set goes on sampling.  (A DEVICE error during the
+ * upload of a set that passed every check -- none is known to occur -- returns the HIP error code and leaves NO set registered: the
+ * old one had to go before the new one could be written.)  Scalars are not part of a
+ * checkpoint (save_state): download the values and set them again.  csrc/sph_scalars.hip describes the kernels.
+ * ==================================================================================== */
+#define SPH_SCALARS_MAX_CHANNELS 4
+#define SPH_SCALARS_MAX_SOURCES 8
+#define SPH_SCALARS_SCALE_LOG2 32
+typedef struct SphScalarParams {
+    int32_t K;                      /* channels, 1 .. SPH_SCALARS_MAX_CHANNELS; 0 clears the set */
+    float kappa[SPH_SCALARS_MAX_CHANNELS];   /* diffusivity per channel, m^2/s, >= 0 */
+    int32_t every;                  /* >= 1: every every-th step of the context is sampled, with a = dt * every * kappa */
+    SphSampleSelect select;         /* the carriers */
+    int32_t n_sources;              /* 0 .. SPH_SCALARS_MAX_SOURCES */
+    int32_t source_object[SPH_SCALARS_MAX_SOURCES];
+    double source_value[SPH_SCALARS_MAX_SOURCES][SPH_SCALARS_MAX_CHANNELS];
+} SphScalarParams;
+typedef struct SphScalarInfo {
+    int32_t K;                      /* of the registered set (0: no set) */
+    int32_t every;
+    int64_t ids;                    /* n_ids of the set */
+    int64_t samples, steps_seen;
+    int64_t overshoot[SPH_SCALARS_MAX_CHANNELS], saturated[SPH_SCALARS_MAX_CHANNELS];
+} SphScalarInfo;
+int32_t sph_scalars_set(SphContext* ctx, const double* values /* host, [n_ids][K], id order; NULL: zeros */, int64_t n_ids,
+                        const SphScalarParams* params);                 /* K == 0 clears; synchronises */
+int32_t sph_scalars_sample(SphContext* ctx);                            /* one sample of the current state; enqueues */
+int32_t sph_scalars_info(SphContext* ctx, SphScalarInfo* info);         /* synchronises when a set is registered */
+int32_t sph_scalars_download(SphContext* ctx, int64_t* raw /*[n_ids][K]*/, double* values /*[n_ids][K]*/, int64_t n_ids);   /* synchronises */
+int32_t sph_scalars_paint(SphContext* ctx, int32_t channel, float lo, float hi, const int32_t* lut /* host, 256 x 3 */);   /* enqueues */
+
 #ifdef __cplusplus
 }
 #endif

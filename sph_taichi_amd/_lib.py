@@ -196,6 +196,22 @@ class SphLoadInfo(C.Structure):
     _fields_ = [("n_objects", C.c_int32), ("every", C.c_int32), ("samples", C.c_int64), ("dropped", C.c_int64), ("steps_seen", C.c_int64)]
 
 
+SCALARS_MAX_CHANNELS, SCALARS_MAX_SOURCES, SCALARS_SCALE_LOG2 = 4, 8, 32
+
+
+class SphScalarParams(C.Structure):
+    """Mirror of `struct SphScalarParams` (include/sph_hip.h)."""
+    _fields_ = [("K", C.c_int32), ("kappa", C.c_float * SCALARS_MAX_CHANNELS), ("every", C.c_int32), ("select", SphSampleSelect),
+                ("n_sources", C.c_int32), ("source_object", C.c_int32 * SCALARS_MAX_SOURCES),
+                ("source_value", (C.c_double * SCALARS_MAX_CHANNELS) * SCALARS_MAX_SOURCES)]
+
+
+class SphScalarInfo(C.Structure):
+    """Mirror of `struct SphScalarInfo` (include/sph_hip.h)."""
+    _fields_ = [("K", C.c_int32), ("every", C.c_int32), ("ids", C.c_int64), ("samples", C.c_int64), ("steps_seen", C.c_int64),
+                ("overshoot", C.c_int64 * SCALARS_MAX_CHANNELS), ("saturated", C.c_int64 * SCALARS_MAX_CHANNELS)]
+
+
 TRACERS_MAX = 1 << 22
 
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
@@ -355,6 +371,11 @@ SYMBOLS = [
     ("sph_loads_info", C.c_int32, [_ctx, C.POINTER(SphLoadInfo)]),
     ("sph_loads_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     ("sph_loads_reset", C.c_int32, [_ctx]),
+    ("sph_scalars_set", C.c_int32, [_ctx, C.c_void_p, C.c_int64, C.POINTER(SphScalarParams)]),
+    ("sph_scalars_sample", C.c_int32, [_ctx]),
+    ("sph_scalars_info", C.c_int32, [_ctx, C.POINTER(SphScalarInfo)]),
+    ("sph_scalars_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_int64]),
+    ("sph_scalars_paint", C.c_int32, [_ctx, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
 ]
 
 _LIB = None

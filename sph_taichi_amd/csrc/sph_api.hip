@@ -436,6 +436,7 @@ int32_t sph_destroy(SphContext* c) {
     sph_tracers_release(c);
     sph_stats_release(c);
     sph_loads_release(c);
+    sph_scalars_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
@@ -966,6 +967,10 @@ static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_st
         }
         if (c->stats_set) {   // a registered statistics set samples x(t_k), v(t_k) every `every`-th step (sph_hip.h, "Running flow statistics")
             rc = sph_stats_step(c);
+            if (rc) return rc;
+        }
+        if (c->scalars) {   // a registered scalar set diffuses at x(t_k) through the cell array of this sort every `every`-th step (sph_hip.h, "Carried scalars")
+            rc = sph_scalars_step(c);
             if (rc) return rc;
         }
         rc = body(c, ev, dynamic_ids, n_dynamic, it + 1 == n_steps);

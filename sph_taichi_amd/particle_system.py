@@ -117,6 +117,7 @@ class ParticleSystem:
         self.tracers = None      # the registered tracer set (tracers.Tracers): None until set_tracers
         self.statistics = None   # the registered statistics set (stats.Statistics): None until set_statistics
         self.loads = None        # the registered load set (loads.Loads): None until set_loads
+        self.scalars = None      # the registered scalar set (scalars.Scalars): None until set_scalars
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -527,6 +528,26 @@ class ParticleSystem:
         from . import loads as _loads
         _loads.clear_loads(self)
         self.loads = None
+
+    def set_scalars(self, channels=("dye",), diffusivity=(1e-4,), values=None, sources=None, every=1, material="fluid", objects=None):
+        """Register carried scalars: 1 to 4 named `channels` that ride on the selected particles (`material`, `objects`: the
+        carriers) and diffuse between neighbouring carriers with `diffusivity` (m^2/s per channel) on the device, every `every`-th
+        step of the device loop (`solver.step(n)`, WCSPH or DFSPH) right behind its sort, with a = dt * every * diffusivity.
+        `values`: None (zeros), an array [n_ids, K] by persistent id, or {object id: row}; `sources`: {object id: row} of up to 8
+        objects (fluid or solid) that hold a prescribed value; every other particle is invisible to the sum (insulation).
+        Replaces the set; returns `self.scalars` (scalars.Scalars): values(), raw(), total(channel), range(channel), overshoot(),
+        saturated(), samples, paint(channel, range=None, colormap="heat"), save(path), sample().  Positions and velocities of
+        a run with a set are bit-identical to the run without.  Scalars are not part of `save_state`."""
+        from . import scalars as _scalars
+        self.scalars = _scalars.set_scalars(self, channels=channels, diffusivity=diffusivity, values=values, sources=sources, every=every,
+                                            material=material, objects=objects)
+        return self.scalars
+
+    def clear_scalars(self):
+        """Remove the scalar set: the steps enqueue what they did before any was set.  `self.scalars` becomes None."""
+        from . import scalars as _scalars
+        _scalars.clear_scalars(self)
+        self.scalars = None
 
     def _step_call(self, name, n_steps, ids, n_ids, dt):
         """sph_step / sph_dfsph_step; with tracers registered, the times of the history frames the call stored are noted."""

@@ -55,6 +55,11 @@ A Configuration with "loads": {"objects": [1], "about": [x, y, z], "every": 1, "
 loads after initialize() (loads.py): every `every`-th step samples the force and torque of the fluid on each listed solid object on
 the device inside the step, and `{scene}_output/loads.csv` at the end of the run holds the series (one row per sample and object);
 `--loads out.csv` writes the same file there as well.
+A Configuration with "scalars": {"channels": ["dye"], "diffusivity": [1e-4], "values": {"0": [1.0]}, "sources": {"1": [350.0]},
+"every": 10, "material": "fluid", "objects": [...], "paint": {"channel": 0, "range": [lo, hi], "colormap": "heat"}} (every key optional)
+registers carried scalars after initialize() (scalars.py): they diffuse on the device inside the step, `{scene}_output/scalars_{cnt:06}.npz`
+per exported interval holds ids and values, and with "paint" every exported frame shows the participants in the table colour of
+their value; `--scalars DIR` writes the same files into DIR as well.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -103,6 +108,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write the running flow statistics of the scene's \"statistics\" grid here after the last frame (legacy binary VTK volume)")
     ap.add_argument("--loads", default="", metavar="PATH",
                     help="write the force / torque series of the scene's \"loads\" objects here after the last frame (CSV)")
+    ap.add_argument("--scalars", default="", metavar="DIR",
+                    help="write the values of the scene's \"scalars\" per exported interval into DIR as well (npz of ids and values)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
                     help="write the column map's surface elevation as an 8-bit grey PNG per exported interval into DIR")
     ap.add_argument("--image_size", type=int, nargs=2, default=[1024, 1024], metavar=("W", "H"),
@@ -153,8 +160,14 @@ def main(argv=None):
     loads_spec = _loads.loads_config(config)           # "loads": None when the key is absent
     if args.loads and loads_spec is None:
         raise ValueError('--loads needs a "loads" object in the scene\'s Configuration')
+    from . import scalars as _scalars
+    scalars_spec = _scalars.scalars_config(config)     # "scalars": None when the key is absent
+    if args.scalars and scalars_spec is None:
+        raise ValueError('--scalars needs a "scalars" object in the scene\'s Configuration')
+    if scalars_spec is not None and args.scalars:
+        os.makedirs(args.scalars, exist_ok=True)
     if (output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None
-            or stats_spec is not None or loads_spec is not None):
+            or stats_spec is not None or loads_spec is not None or scalars_spec is not None):
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -190,6 +203,8 @@ def main(argv=None):
         ps.set_statistics(**stats_spec)
     if loads_spec is not None:
         ps.set_loads(**loads_spec)
+    if scalars_spec is not None:
+        ps.set_scalars(**scalars_spec[0])
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
     probes_out = open(args.probes, "w") if probes_spec is not None else None
@@ -203,6 +218,7 @@ def main(argv=None):
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
     cnt = cnt_ply = frames_written = particle_files = grid_files = mesh_files = tracer_files = 0
+    scalar_files = 0
     render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
@@ -233,6 +249,14 @@ def main(argv=None):
         if tracers_spec is not None and cnt % output_interval == 0:
             ps.tracers.write_vtk(f"{scene_name}_output/tracers_{cnt:06}.vtk")
             tracer_files += 1
+        if scalars_spec is not None and cnt % output_interval == 0:
+            ps.scalars.save(f"{scene_name}_output/scalars_{cnt:06}.npz")
+            if args.scalars:
+                ps.scalars.save(os.path.join(args.scalars, f"scalars_{cnt:06}.npz"))
+            scalar_files += 1
+            paint = scalars_spec[1]
+            if paint is not None and output_frames:          # before the frame: the participants in the colour of their value
+                ps.scalars.paint(paint["channel"], range=paint["range"], colormap=paint["colormap"])
         if probes_out is not None and cnt % output_interval == 0:
             probes = ps.sample_points(**probes_spec)
             probes_out.write(json.dumps({"frame": cnt, "time": probes.time, "probes": probes.rows()}) + "\n")
@@ -313,6 +337,10 @@ def main(argv=None):
         ps.loads.write_csv(f"{scene_name}_output/loads.csv")
         if args.loads:
             ps.loads.write_csv(args.loads)
+    if scalars_spec is not None:
+        info = ps.scalars.info()
+        report["scalars"] = {"channels": list(ps.scalars.channels), "every": info.every, "samples": info.samples, "steps_seen": info.steps_seen,
+                             "overshoot": info.overshoot, "saturated": info.saturated, "files_written": scalar_files}
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
