@@ -244,6 +244,22 @@ class Oracle:
     def set_threads(self, n):
         self.s.omp_threads = int(n)
 
+    def set_solver_attrs(self, viscosity=None, surface_tension=None, stiffness=None, exponent=None, g=None):
+        """The solver's plain attributes (sph_base.py:13-15, WCSPH.py:9-15) changed between two steps: what the reference's
+        kernels read at their next launch, with the viscosity constant folded again as at construction."""
+        s = self.s
+        if viscosity is not None:
+            s.viscosity = float(viscosity)
+            s.visc_d_nu = kernel_constants(float(s.support_radius), s.viscosity)["visc_d_nu"]
+        if surface_tension is not None:
+            s.surface_tension = float(surface_tension)
+        if stiffness is not None:
+            s.stiffness = float(stiffness)
+        if exponent is not None:
+            s.exponent = float(exponent)
+        if g is not None:
+            s.g = _F3(*[float(v) for v in g])
+
     def _p(self):
         return C.byref(self.s)
 
