@@ -1240,6 +1240,114 @@ int32_t sph_scalars_info(SphContext* ctx, SphScalarInfo* info);         /* synch
 int32_t sph_scalars_download(SphContext* ctx, int64_t* raw /*[n_ids][K]*/, double* values /*[n_ids][K]*/, int64_t n_ids);   /* synchronises */
 int32_t sph_scalars_paint(SphContext* ctx, int32_t channel, float lo, float hi, const int32_t* lut /* host, 256 x 3 */);   /* enqueues */
 
+/* ======================================================================================
+ * Particle features (the reference has none): a context may hold ONE registered feature set, for which it evaluates the flow AT THE
+ * PARTICLES THEMSELVES -- vorticity, velocity divergence, the colour gradient (a raw surface normal), the kernel fill, the neighbour
+ * counts and a free-surface flag -- inside the step, ON THE DEVICE, one 64-byte row per persistent id.  WCSPH only.
+ * THE SET.  TARGETS are the records selected by `select` (as in "Field sampling": a material, -1 = any, and up to 32 object ids, 0 =
+ * all).  CANDIDATES of target i are the records j of the 27 cells around the cell the sort hashed i into (its clamped cell
+ * coordinates), read through the cell array, runs clipped to [0, N], of EVERY material and object (a record that is no target is a
+ * candidate all the same).
+ * TERM BY TERM.  The pair geometry of "Field sampling" taken verbatim (f32: d_a = x_i,a - x_j,a; r2 = (dx*dx + dy*dy) + dz*dz;
+ * r = sqrtf(r2) correctly rounded; q = r * inv_h, inv_h = 1.f / support_radius); a pair contributes iff q <= 1.0f and r > 1e-5f
+ * (which excludes i itself; a pair that a rounding error puts outside the 27 cells although its q <= 1.0f does not contribute).
+ * P(q) is the kernel polynomial of "Field sampling" in f32 with k_w = 1: q <= 0.5f ? (6.f*q3 - 6.f*q2) + 1.f : 2.f * ((t*t)*t),
+ * q2 = q*q, q3 = q2*q, t = 1.f - q.  Then in f64 from those f32 values, every operation an IEEE multiply, divide or subtract, nothing
+ * contracted, no f32 divide, no reciprocal (the rules of "Fluid loads"; h = support_radius, k_w and k_dw the context's f32
+ * parameters, each converted):
+ *     V_j  = fluid material ? (double)m_j / (double)rho_j : (double)m_V_j          (rho_j: the density this step computed)
+ *     g    = q <= 0.5 ? q * (3.0 * q - 2.0) : -((1.0 - q) * (1.0 - q))           (as in "Fluid loads")
+ *     gW_b = ((k_dw * g) / (r * h)) * d_b
+ *     fill term   V_j * (k_w * P)                              clamp 2^14, scale 2^30 (SPH_FEATURES_FILL_SCALE_LOG2)
+ *     N_b  term   V_j * gW_b                                   clamp 2^20, scale 2^24 (SPH_FEATURES_SCALE_LOG2), every material
+ *     G_ab term   (V_j * (double)(v_j,a - v_i,a)) * gW_b       clamp 2^20, scale 2^24, FLUID candidates only; the difference in f32
+ * each term f: c = fmin(fmax(f, -limit), limit); saturated += (c != f); sum += llrint(c * scale).  A NaN ends at -limit and is
+ * counted.  The fill has one more term, the target's own: V_i * (k_w * 1.0), clamped and rounded alike.  n_fluid and n_solid count the
+ * contributing pairs with a fluid and with any other candidate.  G_ab is d v_a / d x_b in DIFFERENCE form without renormalisation:
+ * exact for a uniform flow, first order only where the kernel support is full.
+ * OVERFLOW BUDGET: a term is at most 2^44 in magnitude: 2^18 pair terms AT THE CLAMP still fit an i64, sums of three or differences of
+ * two of them included.  DETERMINISTIC: every accumulation is an integer add (lane sums, DPP row sums; the only atomics are integer
+ * adds on the target list's count), so a row is one function of the sampled state, whatever the lane split or the launch order.
+ * There is no float or double atomic.
+ * THE ROW (SphFeatureRow, stored BY PERSISTENT ID, not in sorted order; a row outside the selection is all zero).  Every float is
+ * (float)((double)I / 2^s) of an integer sum I or of an integer sum or difference of such sums:
+ *     vorticity = (G_zy - G_yz, G_xz - G_zx, G_yx - G_xy);   divergence = (G_xx + G_yy) + G_zz;   normal = N (raw: it points INTO the
+ *     fluid; the host normalises and flips it);   fill;   n_fluid, n_solid;   x = the f32 position at the sample;
+ *     flags: SPH_FEATURE_VALID (the particle was a target), SPH_FEATURE_SURFACE, SPH_FEATURE_SATURATED (a term of it was clamped).
+ * SURFACE: n_fluid + n_solid < min_neighbours, or, when normal_min > 0, (h*h) * ((Nx*Nx + Ny*Ny) + Nz*Nz) > normal_min * normal_min in
+ * f64 with N_b = (double)I_b / 2^24.  The default min_neighbours = 24 comes from the rest lattice of spacing d with h = 2 d: a face
+ * particle has at most 22 neighbours, any particle one layer in at least 26 even when every pair at exactly r = 2 d rounds outside
+ * the support; 24 separates the two whichever way those pairs round.
+ * THE HOOK: while a set is registered, every step of sph_step (and of sph_sweeps) is counted (steps_seen, from 0 at registration), and
+ * step k is SAMPLED iff steps_seen % every == 0 before it is counted.  The sample is enqueued directly behind the step's density and
+ * equation of state and before its force sweep: positions x(t_k), velocities v(t_k), this step's sort and density.  Density and the
+ * id of a fused step are materialised in the particle record first (the values every later reader would get anyway).  Two clears (the
+ * 4-byte target count, the rows) and two launches per sampled step on the context's stream, no synchronisation, nothing crosses to
+ * the host.  Only the LATEST sample is kept, with its time and its step index k; there is no history.  With no set registered (never
+ * set, or cleared) the step enqueues exactly what it enqueues without this section.  While a set is registered SPH_OPT_SORT_LEAN is
+ * not taken (the sample reads the particle record), as with a load set; positions and velocities of a run with a set are
+ * bit-identical to the run without.  sph_dfsph_step with a registered set returns SPH_E_STATE (WCSPH only, the precedent of the
+ * load set).  COST: a 27-cell walk of every fluid particle with thirteen f64 terms per pair -- more than a carried-scalar sample, which
+ * costs several steps' time -- so `every` > 1 is the normal use (profiles/features_timing.json once measured).
+ * sph_features_sample takes ONE sample of the current state outside a step -- for callers that drive the kernels stage by stage --
+ * with whatever density the particle record holds; it needs the neighbour structure of the current positions
+ * (sph_initialize_particle_system) and does not touch steps_seen; its step index is the current steps_seen.
+ * sph_features_set REPLACES the set, zeroes rows and counters and synchronises; NULL clears the set (and frees nothing).  The row
+ * count is the context's id capacity.  sph_features_info returns host data only (step = -1 before the first sample).
+ * sph_features_download copies the rows, n_rows being exactly the info's, synchronises, then checks the device's error flags.
+ * sph_features_paint(ctx, field, lo, hi, lut): one streaming pass that writes, for every live record whose row of the latest sample is
+ * valid, the table colour of the row's field into the object colour of its id (SPH_F_COLOR, which both frame styles draw), and
+ * nothing else.  s (f32) is: SPH_FEATURE_FIELD_VORTICITY sqrtf((wx*wx + wy*wy) + wz*wz); _DIVERGENCE; _FILL; _NEIGHBOURS
+ * (float)(n_fluid + n_solid); _SURFACE 1.f or 0.f; then the index arithmetic of "Field colouring" verbatim -- t = (s - lo) * inv,
+ * inv = 1.f / (hi - lo); t = t >= 0 ? min(t, 1) : 0; idx = int(t * 255 + 0.5) -- and colour[c] = lut[idx][c], lut 256 x 3 int32 in
+ * [0, 255].  An explicit call; other records keep their colour.  Enqueues.
+ * Buffers (a target list of the context's record capacity, the rows, the table) are allocated by the first set, grow only and are
+ * freed with the context; a context that never sets features allocates nothing.
+ * TEST AID: the environment variable SPH_FEATURES_BLOCKS = b >= 1, read by sph_features_set, caps the gather's grid at b blocks of
+ * sixteen rows (it can only shrink the grid; results are the same words).  Not for production use.
+ * SPH_E_INVALID: a selection out of range; every < 1; min_neighbours outside [0, 2^20]; normal_min negative or not finite; a download
+ * with another n_rows; paint: a field outside [0, SPH_FEATURE_FIELDS), lo or hi not finite, lo >= hi, a reciprocal width that is not
+ * a positive finite f32, a NULL table or an entry outside [0, 255].  SPH_E_STATE: a sample, download or paint without a registered
+ * set; a sample without the neighbour structure; sph_dfsph_step with a registered set; a slab rank (every entry but info).  A refused
+ * sph_features_set changes nothing.  Features are not part of a checkpoint (save_state).  csrc/sph_features.hip describes the kernels.
+ * ==================================================================================== */
+#define SPH_FEATURES_SCALE_LOG2 24
+#define SPH_FEATURES_FILL_SCALE_LOG2 30
+#define SPH_FEATURE_VALID 1
+#define SPH_FEATURE_SURFACE 2
+#define SPH_FEATURE_SATURATED 4
+enum SphFeatureField { SPH_FEATURE_FIELD_VORTICITY = 0, SPH_FEATURE_FIELD_DIVERGENCE, SPH_FEATURE_FIELD_FILL, SPH_FEATURE_FIELD_NEIGHBOURS,
+                       SPH_FEATURE_FIELD_SURFACE, SPH_FEATURE_FIELDS };
+typedef struct SphFeatureParams {
+    SphSampleSelect select;         /* the targets */
+    int32_t every;                  /* >= 1: every every-th step of the context is sampled */
+    int32_t min_neighbours;         /* surface iff n_fluid + n_solid < min_neighbours (24: the rest lattice, above) */
+    float normal_min;               /* > 0: surface also iff h |N| > normal_min; 0: off */
+} SphFeatureParams;
+typedef struct SphFeatureRow {      /* 64 bytes */
+    float x[3];                     /* the position at the sample */
+    float vorticity[3];             /* 1/s */
+    float divergence;               /* 1/s */
+    float normal[3];                /* the raw colour gradient N, 1/m: into the fluid */
+    float fill;                     /* about 1 inside the fluid at rest */
+    int32_t n_fluid, n_solid;
+    int32_t flags;                  /* SPH_FEATURE_VALID | _SURFACE | _SATURATED */
+    int32_t reserved_[2];           /* zero */
+} SphFeatureRow;
+typedef struct SphFeatureInfo {
+    int32_t every;                  /* of the registered set (0: no set) */
+    int32_t reserved_;
+    int64_t rows;                   /* rows of a download: the context's id capacity */
+    int64_t samples, steps_seen;
+    int64_t step;                   /* step index of the latest sample, -1: none yet */
+    double time;                    /* simulated time of the latest sample */
+} SphFeatureInfo;
+int32_t sph_features_set(SphContext* ctx, const SphFeatureParams* params);   /* NULL clears; synchronises */
+int32_t sph_features_sample(SphContext* ctx);                                /* one sample of the current state; enqueues */
+int32_t sph_features_info(SphContext* ctx, SphFeatureInfo* info);            /* host data only */
+int32_t sph_features_download(SphContext* ctx, void* rows /* SphFeatureRow [n_rows] */, int64_t n_rows);   /* synchronises */
+int32_t sph_features_paint(SphContext* ctx, int32_t field, float lo, float hi, const int32_t* lut /* host, 256 x 3 */);   /* enqueues */
+
 #ifdef __cplusplus
 }
 #endif

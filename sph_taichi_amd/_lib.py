@@ -212,6 +212,28 @@ class SphScalarInfo(C.Structure):
                 ("overshoot", C.c_int64 * SCALARS_MAX_CHANNELS), ("saturated", C.c_int64 * SCALARS_MAX_CHANNELS)]
 
 
+FEATURES_SCALE_LOG2, FEATURES_FILL_SCALE_LOG2 = 24, 30
+FEATURE_VALID, FEATURE_SURFACE, FEATURE_SATURATED = 1, 2, 4
+FEATURE_FIELDS = ("vorticity", "divergence", "fill", "neighbours", "surface")      # enum SphFeatureField
+
+
+class SphFeatureParams(C.Structure):
+    """Mirror of `struct SphFeatureParams` (include/sph_hip.h)."""
+    _fields_ = [("select", SphSampleSelect), ("every", C.c_int32), ("min_neighbours", C.c_int32), ("normal_min", C.c_float)]
+
+
+class SphFeatureRow(C.Structure):
+    """Mirror of `struct SphFeatureRow` (include/sph_hip.h): 64 bytes."""
+    _fields_ = [("x", _F3), ("vorticity", _F3), ("divergence", C.c_float), ("normal", _F3), ("fill", C.c_float),
+                ("n_fluid", C.c_int32), ("n_solid", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32 * 2)]
+
+
+class SphFeatureInfo(C.Structure):
+    """Mirror of `struct SphFeatureInfo` (include/sph_hip.h)."""
+    _fields_ = [("every", C.c_int32), ("reserved_", C.c_int32), ("rows", C.c_int64), ("samples", C.c_int64), ("steps_seen", C.c_int64),
+                ("step", C.c_int64), ("time", C.c_double)]
+
+
 TRACERS_MAX = 1 << 22
 
 # field bits of the field sampling (SPH_SAMPLE_*), its limits and the fixed-point scale 2^30 of its sums
@@ -376,6 +398,11 @@ SYMBOLS = [
     ("sph_scalars_info", C.c_int32, [_ctx, C.POINTER(SphScalarInfo)]),
     ("sph_scalars_download", C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_int64]),
     ("sph_scalars_paint", C.c_int32, [_ctx, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
+    ("sph_features_set", C.c_int32, [_ctx, C.POINTER(SphFeatureParams)]),
+    ("sph_features_sample", C.c_int32, [_ctx]),
+    ("sph_features_info", C.c_int32, [_ctx, C.POINTER(SphFeatureInfo)]),
+    ("sph_features_download", C.c_int32, [_ctx, C.c_void_p, C.c_int64]),
+    ("sph_features_paint", C.c_int32, [_ctx, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
 ]
 
 _LIB = None

@@ -9,7 +9,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["sph_api.hip", "sph_sort.hip", "sph_gather.hip", "sph_integrate.hip", "sph_comm.hip", "sph_render.hip", "sph_diag.hip", "sph_columns.hip", "sph_export.hip", "sph_surface.hip", "sph_sample.hip", "sph_mesh.hip", "sph_tracers.hip", "sph_stats.hip", "sph_loads.hip", "sph_scalars.hip"]
+SOURCES = ["sph_api.hip", "sph_sort.hip", "sph_gather.hip", "sph_integrate.hip", "sph_comm.hip", "sph_render.hip", "sph_diag.hip", "sph_columns.hip", "sph_export.hip", "sph_surface.hip", "sph_sample.hip", "sph_mesh.hip", "sph_tracers.hip", "sph_stats.hip", "sph_loads.hip", "sph_scalars.hip", "sph_features.hip"]
 HEADERS = [os.path.join(CSRC, "sph_internal.h"), os.path.join(CSRC, "sph_derived.h"), os.path.join(CSRC, "sph_setstate.h"), os.path.join(CSRC, "sph_bricks.h"), os.path.join(CSRC, "sph_render_dev.h"), os.path.join(CSRC, "sph_observe.h"), os.path.join(CSRC, "sph_sample_grid.h"), os.path.join(CSRC, "sph_sample_pair.h"), os.path.join(CSRC, "sph_scalars_check.h"), os.path.join(_HERE, "..", "include", "sph_hip.h")]
 LIB = os.path.join(_HERE, "libsph_hip.so")
 # -fno-slp-vectorize: the SLP pass packs the x/y lanes of the distance test into v_pk_*_f32, which on gfx950

@@ -437,6 +437,7 @@ int32_t sph_destroy(SphContext* c) {
     sph_stats_release(c);
     sph_loads_release(c);
     sph_scalars_release(c);
+    sph_features_release(c);
     delete[] c->obj_info;
     for (int s = 0; s < SPH_MAX_TIMED_STEPS; ++s)
         for (int k = 0; k < 5; ++k) if (c->ev[s][k]) (void)hipEventDestroy(c->ev[s][k]);
@@ -838,6 +839,10 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
             rc = sph_loads_step(c);
             if (rc) return rc;
         }
+        if (c->features) {   // a registered feature set samples x(t_k), v(t_k) with this step's rho (sph_hip.h, "Particle features")
+            rc = sph_features_step(c);
+            if (rc) return rc;
+        }
         if (ev) SPH_HIP(c, hipEventRecord(ev[2], c->stream));
         // With the one-gather force sweep no workgroup reads another particle's xm / vf (neighbours come from the
         // stg / gat copies), so each fluid target is integrated right in the sweep's finish and the streaming advect
@@ -859,6 +864,7 @@ static int step_sweeps(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_ids
         rc = sphk_gather(c, GM_NONPRESSURE);
         rc = rc ? rc : sphk_eos(c);
         if (!rc && c->loads) rc = sph_loads_step(c);   // (as above: behind this step's p and rho, before they are used)
+        if (!rc && c->features) rc = sph_features_step(c);   // (likewise)
         rc = rc ? rc : sphk_gather(c, GM_PRESSURE);
         if (rc) return rc;
     }
@@ -937,8 +943,9 @@ typedef int (*StepBody)(SphContext* c, hipEvent_t* ev, const int32_t* dynamic_id
 // need solids, which the pure-fluid rule of the lean scatter excludes, and registered motions are excluded here by name.  The
 // tracers read xm / vf and the cell array only, the running statistics xm / vf only.  A registered load set (sph_loads.hip) reads m,
 // density and pressure of the fluid in aux between the density and the force sweep: a third in-step consumer, excluded by name.
+// A registered feature set (sph_features.hip) reads m, density and the id there at the same point: the fourth, excluded alike.
 static bool step_aux_dead(const SphContext* c, StepBody body) {
-    return body == step_sweeps && c->opt_fused && c->opt_gather_impl == 1 && sphk_brick_sweeps_reach(c) && c->n_kin == 0 && !sph_loads_armed(c);
+    return body == step_sweeps && c->opt_fused && c->opt_gather_impl == 1 && sphk_brick_sweeps_reach(c) && c->n_kin == 0 && !sph_loads_armed(c) && !sph_features_armed(c);
 }
 
 static int step_loop(SphContext* c, const char* who, StepBody body, int32_t n_steps, const int32_t* dynamic_ids, int32_t n_dynamic) {
@@ -1533,6 +1540,9 @@ int32_t sph_dfsph_step(SphContext* c, int32_t n_steps, const int32_t* dynamic_id
     if (sph_loads_armed(c))
         return sph_fail(c, SPH_E_STATE, "sph_dfsph_step: a load set is registered; fluid loads are sampled under WCSPH only (DFSPH couples "
                                         "through velocity changes): call sph_loads_set(ctx, NULL) first");
+    if (sph_features_armed(c))
+        return sph_fail(c, SPH_E_STATE, "sph_dfsph_step: a feature set is registered; particle features are sampled under WCSPH only (as fluid "
+                                        "loads are): call sph_features_set(ctx, NULL) first");
     return step_loop(c, "sph_dfsph_step", dfsph_sweeps, n_steps, dynamic_ids, n_dynamic);
 }
 

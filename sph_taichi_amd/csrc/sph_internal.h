@@ -106,6 +106,7 @@ struct SphTracers;  // passive tracers (sph_tracers.hip): the set's buffers, par
 struct SphStatsSet; // running flow statistics (sph_stats.hip): the registered grid, its scratch and accumulator planes, the counters; null until sph_stats_set
 struct SphLoadSet;  // fluid loads on solid objects (sph_loads.hip): the target list, the history, the set and the counters; null until sph_loads_set
 struct SphScalarSet; // carried scalars (sph_scalars.hip): the per-id store, the snapshot, the carrier list, the set and the counters; null until sph_scalars_set
+struct SphFeatureSet; // per-particle flow features (sph_features.hip): the target list, the by-id rows, the table, the set and the counters; null until sph_features_set
 struct CellIdx16 { int v[16]; };   // up to 16 cell indices whose scanned values the host wants back (slab layer offsets); -1 = unused
 
 struct SphContext {
@@ -226,6 +227,7 @@ struct SphContext {
     SphStatsSet* stats_set;
     SphLoadSet* loads;
     SphScalarSet* scalars;
+    SphFeatureSet* features;
     // kinematic bodies (sph_hip.h, last section): the clock, the registered motions and what the host knows about the objects
     double sim_time;        // simulated time: += dt at the end of every step of sph_step / sph_dfsph_step
     int n_kin;              // registered motions (0: the step calls enqueue nothing extra)
@@ -332,6 +334,9 @@ bool sph_loads_armed(const SphContext* c);  // sph_loads.hip: a load set is regi
 int sph_loads_step(SphContext* c);        // sph_loads.hip: step_sweeps' hook behind density and EOS: counts the step; two launches when a sample is due
 void sph_scalars_release(SphContext* c); // sph_scalars.hip: frees the scalar set's store, snapshot, list, counters and table (sph_destroy)
 int sph_scalars_step(SphContext* c);      // sph_scalars.hip: the step loops' hook behind the sort: counts the step; a 4-byte clear and two launches when a sample is due
+void sph_features_release(SphContext* c); // sph_features.hip: frees the feature set's list, rows and table (sph_destroy)
+bool sph_features_armed(const SphContext* c);  // sph_features.hip: a feature set is registered (its samples read aux inside the step)
+int sph_features_step(SphContext* c);      // sph_features.hip: step_sweeps' hook behind density and EOS: counts the step; two clears and two launches when a sample is due
 
 enum GatherMode {
     GM_BVOL_STATIC = 0,

@@ -68,6 +68,14 @@ static inline int sph_observe_download(SphContext* c, void* host, const void* de
     return sph_check_device_flags(c);
 }
 
+// THE ID OF A RECORD lives in the pid array while a lean scatter keeps the ids apart from aux, and in aux.w otherwise (sph_derived.h):
+// a pointer and a stride (pid: 1; aux: the fourth word of a 16-byte record, stride 4) for kernels that must not ask for the fold
+struct SphIds { const int* ptr; int stride; };
+static inline SphIds sph_observe_ids(const SphContext* c) {
+    if (sphd_pid_apart(c->dv)) return SphIds{c->pid[c->cur] + c->in_off, 1};
+    return SphIds{reinterpret_cast<const int*>(c->aux[c->cur] + c->in_off) + 3, 4};
+}
+
 // A contiguous streaming walk over N > 0 records: block b takes the tiles (`threads` records each) [b, b + 1) * per_block, so
 // that at most `max_blocks` blocks cover them.
 struct SphWalk { int blocks, per_block; };

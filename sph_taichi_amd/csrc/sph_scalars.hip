@@ -249,12 +249,9 @@ void sph_scalars_release(SphContext* c) {
     sph_observe_release(c->scalars, &SphScalarSet::store, &SphScalarSet::snap, &SphScalarSet::list, &SphScalarSet::counters, &SphScalarSet::lut);
 }
 
-struct ScalarIds { const int* ptr; int stride; };
-// where the ids of the current records are (sph_derived.h): nobody is asked to move them
-static ScalarIds scalars_ids(const SphContext* c) {
-    if (sphd_pid_apart(c->dv)) return ScalarIds{c->pid[c->cur] + c->in_off, 1};
-    return ScalarIds{reinterpret_cast<const int*>(c->aux[c->cur] + c->in_off) + 3, 4};
-}
+// where the ids of the current records are (sph_observe.h): nobody is asked to move them
+typedef SphIds ScalarIds;
+static ScalarIds scalars_ids(const SphContext* c) { return sph_observe_ids(c); }
 
 static ScalarRoles scalars_roles(const SphScalarSet* s) {
     ScalarRoles r;

@@ -118,6 +118,7 @@ class ParticleSystem:
         self.statistics = None   # the registered statistics set (stats.Statistics): None until set_statistics
         self.loads = None        # the registered load set (loads.Loads): None until set_loads
         self.scalars = None      # the registered scalar set (scalars.Scalars): None until set_scalars
+        self.features = None     # the registered feature set (features.Features): None until set_features
         self.x_vis_buffer = None
         if self.GGUI:
             self.x_vis_buffer = np.zeros((self.particle_max_num, 3), dtype=np.float32)
@@ -548,6 +549,25 @@ class ParticleSystem:
         from . import scalars as _scalars
         _scalars.clear_scalars(self)
         self.scalars = None
+
+    def set_features(self, every=10, material="fluid", objects=None, min_neighbours=24, normal_min=0.0):
+        """Register per-particle flow features of the selected particles (`material`, `objects`: the selection of the other
+        observers): from now on every `every`-th WCSPH step samples, behind its density and before its force sweep, vorticity,
+        divergence, colour gradient, kernel fill, neighbour counts and a free-surface flag (fewer than `min_neighbours` neighbours, or
+        h |N| above `normal_min` when that is positive) of each of them on the device, one row per persistent id, the latest sample
+        only.  A sample walks the 27 cells of every selected particle -- several steps' time -- so `every` > 1 is the normal use.
+        Replaces the set; returns `self.features` (features.Features): vorticity(), divergence(), fill(), neighbours(), normal(),
+        surface(), valid(), saturated(), positions(), ids, time, step, samples, enstrophy(), sample(), write_ply(), paint()."""
+        from . import features as _features
+        self.features = _features.set_features(self, every=every, material=material, objects=objects, min_neighbours=min_neighbours,
+                                               normal_min=normal_min)
+        return self.features
+
+    def clear_features(self):
+        """Remove the feature set: the steps enqueue what they did before any was set.  `self.features` becomes None."""
+        from . import features as _features
+        _features.clear_features(self)
+        self.features = None
 
     def _step_call(self, name, n_steps, ids, n_ids, dt):
         """sph_step / sph_dfsph_step; with tracers registered, the times of the history frames the call stored are noted."""

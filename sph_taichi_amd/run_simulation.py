@@ -60,6 +60,13 @@ A Configuration with "scalars": {"channels": ["dye"], "diffusivity": [1e-4], "va
 registers carried scalars after initialize() (scalars.py): they diffuse on the device inside the step, `{scene}_output/scalars_{cnt:06}.npz`
 per exported interval holds ids and values, and with "paint" every exported frame shows the participants in the table colour of
 their value; `--scalars DIR` writes the same files into DIR as well.
+A Configuration with "features": {"every": 10, "material": "fluid", "objects": [0], "minNeighbours": 24, "normalMin": 0.0,
+"export": "surface" | "all", "fields": [...], "paint": {"field": "vorticity", "range": [lo, hi], "colormap": "heat"}} (every key
+optional) registers per-particle flow features after initialize() (features.py): every `every`-th step evaluates vorticity,
+divergence, surface normal, kernel fill, neighbour counts and a free-surface flag at the particles on the device inside the step;
+with "export", `{scene}_output/features_{cnt:06}.ply` per exported interval holds the latest sample (the surface shell alone, or
+every target), and with "paint" every exported frame shows the targets in the table colour of that field; `--features DIR` writes
+the same files into DIR as well.
 `output_interval` stays the reference's expression on the configured `timeStepSize`.
 """
 from __future__ import annotations
@@ -108,6 +115,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write the running flow statistics of the scene's \"statistics\" grid here after the last frame (legacy binary VTK volume)")
     ap.add_argument("--loads", default="", metavar="PATH",
                     help="write the force / torque series of the scene's \"loads\" objects here after the last frame (CSV)")
+    ap.add_argument("--features", default="", metavar="DIR",
+                    help="write the per-particle feature files of the scene's \"features\" per exported interval into DIR as well (PLY)")
     ap.add_argument("--scalars", default="", metavar="DIR",
                     help="write the values of the scene's \"scalars\" per exported interval into DIR as well (npz of ids and values)")
     ap.add_argument("--heightmap_dir", default="", metavar="DIR",
@@ -166,8 +175,14 @@ def main(argv=None):
         raise ValueError('--scalars needs a "scalars" object in the scene\'s Configuration')
     if scalars_spec is not None and args.scalars:
         os.makedirs(args.scalars, exist_ok=True)
+    from . import features as _features
+    features_spec = _features.features_config(config)  # "features": None when the key is absent
+    if args.features and features_spec is None:
+        raise ValueError('--features needs a "features" object in the scene\'s Configuration')
+    if features_spec is not None and args.features:
+        os.makedirs(args.features, exist_ok=True)
     if (output_ply or output_obj or export_spec is not None or grid_spec is not None or mesh_spec is not None or tracers_spec is not None
-            or stats_spec is not None or loads_spec is not None or scalars_spec is not None):
+            or stats_spec is not None or loads_spec is not None or scalars_spec is not None or features_spec is not None):
         os.makedirs(f"{scene_name}_output", exist_ok=True)
     invisible_objects = config.get_cfg("invisibleObjects") or []
     camera = surface_style = None
@@ -205,6 +220,8 @@ def main(argv=None):
         ps.set_loads(**loads_spec)
     if scalars_spec is not None:
         ps.set_scalars(**scalars_spec[0])
+    if features_spec is not None:
+        ps.set_features(**features_spec[0])
     controller = ps.build_time_step_controller(solver) if config.get_cfg("adaptiveTimeStep") is not None else None
     diag_out = open(args.diagnostics, "w") if args.diagnostics else None
     probes_out = open(args.probes, "w") if probes_spec is not None else None
@@ -218,7 +235,7 @@ def main(argv=None):
             os.makedirs(args.heightmap_dir, exist_ok=True)
 
     cnt = cnt_ply = frames_written = particle_files = grid_files = mesh_files = tracer_files = 0
-    scalar_files = 0
+    scalar_files = feature_files = 0
     render_s = export_s = 0.0
     t0 = time.perf_counter()
     for _ in range(args.frames):
@@ -257,6 +274,16 @@ def main(argv=None):
             paint = scalars_spec[1]
             if paint is not None and output_frames:          # before the frame: the participants in the colour of their value
                 ps.scalars.paint(paint["channel"], range=paint["range"], colormap=paint["colormap"])
+        if features_spec is not None and cnt % output_interval == 0 and ps.features.info().samples > 0:
+            out = features_spec[1]
+            if out["export"] is not None:
+                name = f"features_{cnt:06}.ply"
+                for d in [f"{scene_name}_output"] + ([args.features] if args.features else []):
+                    ps.features.write_ply(os.path.join(d, name), surface_only=out["export"] == "surface", fields=out["fields"])
+                feature_files += 1
+            paint = out["paint"]
+            if paint is not None and output_frames:          # before the frame: the targets in the colour of the field
+                ps.features.paint(paint["field"], range=paint["range"], colormap=paint["colormap"])
         if probes_out is not None and cnt % output_interval == 0:
             probes = ps.sample_points(**probes_spec)
             probes_out.write(json.dumps({"frame": cnt, "time": probes.time, "probes": probes.rows()}) + "\n")
@@ -341,6 +368,10 @@ def main(argv=None):
         info = ps.scalars.info()
         report["scalars"] = {"channels": list(ps.scalars.channels), "every": info.every, "samples": info.samples, "steps_seen": info.steps_seen,
                              "overshoot": info.overshoot, "saturated": info.saturated, "files_written": scalar_files}
+    if features_spec is not None:
+        info = ps.features.info()
+        report["features"] = {"every": info.every, "samples": info.samples, "steps_seen": info.steps_seen, "step": info.step,
+                              "time": info.time, "files_written": feature_files}
     if frames_written:
         report["frames_written"] = frames_written
         report["render_ms_per_frame"] = round(render_s / frames_written * 1e3, 4)
